@@ -10,6 +10,16 @@ Usage (driver): python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 Single process: python bench.py [--gpus 1] [--steps K] [--warmup W]
 
+A plain run does only what the headline figure needs: set up, warm up, time
+K steps, print the result line. --dump-outputs DIR additionally writes what
+the last timed step computed (DIR/<name>.npy, float32) so two builds can be
+compared output for output; inputs and initial weights are seeded, so the
+same arguments give the same inputs on every run, and the last timed step
+of a dumping run starts again from the seeded weights and a fresh optimizer
+state, so the dump does not depend on how the earlier steps' rounding noise
+was amplified by training. --full is where any
+measurement beyond the headline figure belongs (none at present).
+
 One training step = forward + loss + backward (+ DP all-reduce) + Adam step.
 Timed region: barrier + synchronize, K steps, barrier + synchronize; elapsed
 is MAX over ranks; rank 0 prints ONE JSON line.
@@ -39,6 +49,56 @@ DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 BASELINE_FLOOR = {"bench-1024": 1198.0}
 
 
+def dump_outputs(out_dir, last, model, infer):
+    """Write what the last timed step handed back, one float32 .npy each:
+    the prediction and, for a training step, the loss, the gradients and the
+    updated parameters (both flattened in model.parameters() order)."""
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts])
+
+    out = {"pred": last["pred"]}
+    if not infer:
+        params = list(model.parameters())
+        out["loss"] = last["loss"].reshape(1)
+        out["grads"] = flat([p.grad for p in params if p.grad is not None])
+        out["params"] = flat(params)
+    # 64 MB in all; every preset is far below it (a few M parameters)
+    total = sum(4 * t.numel() for t in out.values())
+    assert total <= 64 * 2**20, f"outputs too large to dump: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.detach().float().cpu().numpy())
+
+
+def make_state_reset(model, opt):
+    """Snapshot the seeded weights (call before any step); the returned
+    function puts weights and optimizer state back in place, keeping every
+    storage where a captured graph expects it."""
+    params = list(model.parameters())
+    fused = hasattr(opt, "arena")
+    if fused:                       # FusedAdam: params are views of one arena
+        arena0, hyper0 = opt.arena.clone(), opt.hyper.clone()
+    else:
+        init = [p.detach().clone() for p in params]
+
+    @torch.no_grad()
+    def reset():
+        if fused:
+            opt.arena.copy_(arena0)
+            opt.master.copy_(arena0)
+            opt.m.zero_()
+            opt.v.zero_()
+            opt.hyper.copy_(hyper0)
+        else:
+            torch._foreach_copy_(params, init)
+            for st in opt.state.values():   # step, exp_avg, exp_avg_sq
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+    return reset
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -56,6 +116,13 @@ def main():
     p.add_argument("--mode", type=str, default="train", choices=["train", "infer"],
                    help="train: fwd+loss+bwd+opt (the driver contract); "
                         "infer: eval-mode forward only (the serving path)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the last step's outputs "
+                        "(loss, pred, grads, params; infer: pred) to "
+                        "DIR/<name>.npy as float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure "
+                        "(none at present; a plain run times the steps only)")
     args = p.parse_args()
 
     if args.impl:
@@ -123,21 +190,46 @@ def main():
     if infer:
         model.eval()
 
+    # --dump-outputs: the float-atomic accumulation in the kernels makes two
+    # runs differ in the last bits of every step, and training (Adam moves a
+    # weight by ~lr whatever the gradient's size) amplifies that from step to
+    # step. So that the dump is a function of the seeded inputs alone, the
+    # LAST timed step starts from the seeded weights and a fresh optimizer
+    # state again; a plain run never resets anything.
+    reset_state = (make_state_reset(model, opt)
+                   if args.dump_outputs and not infer else None)
+
+    # --dump-outputs: what the latest step() computed, as detached aliases
+    # (holding the loss itself would keep its autograd graph, and with it the
+    # previous step's AccumulateGrad nodes and their stream, alive into the
+    # next step and into hipGraph capture). Under graph replay these are the
+    # captured static tensors, refreshed in place by every replay.
+    last = {}
+
+    def keep(**outs):
+        if args.dump_outputs:
+            for k, v in outs.items():
+                last[k] = v.detach()
+
     def step():
         if infer:
             with torch.no_grad():
-                return model(x, adjs)
+                pred = model(x, adjs)
+            keep(pred=pred)
+            return pred
         if reducer is not None:
             reducer.zero_grad()
         else:
             opt.zero_grad(set_to_none=False)
-        loss = criterion(model(x, adjs), y)
+        pred = model(x, adjs)
+        loss = criterion(pred, y)
         loss.backward()
         if reducer is not None:
             reducer.reduce()
         elif hip_mode and world > 1:
             opt.reduce()
         opt.step()
+        keep(pred=pred, loss=loss)
         return loss
 
     def barrier_sync():
@@ -187,7 +279,10 @@ def main():
         prof_ctx.__enter__()
 
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1 if reset_state else args.steps):
+        run_step()
+    if reset_state:
+        reset_state()
         run_step()
     barrier_sync()
     elapsed = time.perf_counter() - t0
@@ -196,6 +291,9 @@ def main():
         prof_ctx.__exit__(None, None, None)
         if rank == 0:
             prof_ctx.export_chrome_trace(args.profile_trace)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model, infer)
 
     # impl truthfulness: if any op fell back to torch under
     # STMGCN_ALLOW_FALLBACK=1, the JSON must not claim a pure-hip run

@@ -40,6 +40,54 @@ def test_bench_json_contract():
     assert cfg["global_batch"] == 32 and cfg["parallelism"] == "dp1"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy;
+    the same arguments give the same inputs, hence (on CPU, bit-for-bit) the
+    same outputs; --full is accepted and keeps the one-line contract."""
+    import numpy as np
+    import torch
+    # the flagship config where there is a GPU, the CPU plumbing config else
+    gpu = torch.cuda.is_available()
+    preset, batch = ("bench-1024", 32) if gpu else ("cpu-small", 8)
+    dumps = []
+    for name, extra in [("a", ()), ("b", ("--full",))]:
+        d = tmp_path / name
+        rec = _run_bench("--preset", preset, "--dump-outputs", str(d), *extra)
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == {"loss", "pred", "grads", "params"}
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        if not gpu:
+            np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    if gpu:
+        # The HIP kernels accumulate in fp32 with atomics, so two GPU runs
+        # differ in summation order: no bitwise check there. The dumped step
+        # starts from the seeded weights, so only that one step's noise shows.
+        for k in a:
+            print(k, "max|a|=%g max|a-b|=%g" % (np.abs(a[k]).max(),
+                                                np.abs(a[k] - b[k]).max()))
+        ulp = 2.0 ** -8                                   # bf16
+        # loss: mean over 32k targets ~N(0,1) of (pred - y)^2, |pred| << 1:
+        # agrees to the rounding of the returned value, one ulp either side
+        np.testing.assert_allclose(a["loss"], b["loss"], rtol=2 * ulp)
+        # pred: an fp32 sum that lands on the other side of a bf16 rounding
+        # boundary moves a stored value by one ulp; between the atomically
+        # summed gate statistic and the prediction lie the gate, three LSTM
+        # layers, the graph conv and the head: at most 8 ulps of the largest
+        np.testing.assert_allclose(a["pred"], b["pred"], rtol=0,
+                                   atol=8 * ulp * float(np.abs(a["pred"]).max()))
+        # params: one Adam step from identical weights moves each weight by
+        # at most lr = 2e-3, whatever its gradient; plus the bf16 store
+        np.testing.assert_allclose(
+            a["params"], b["params"], rtol=0,
+            atol=2 * 2e-3 + ulp * float(np.abs(a["params"]).max()))
+    assert a["loss"].shape == (1,) and a["pred"].shape[0] == batch
+    assert a["grads"].shape == a["params"].shape and np.abs(a["grads"]).max() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+
+
 def test_bench_torch_floor_mode():
     rec = _run_bench("--impl", "torch")
     assert rec["config"]["impl"].startswith("torch")

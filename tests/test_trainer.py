@@ -136,7 +136,7 @@ def test_main_cli_end_to_end(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out_dir = tmp_path / "output"
     r = subprocess.run(
-        [sys.executable, os.path.join(repo, "Main.py"),
+        [sys.executable, os.path.join(repo, "Main.py"), "-device", "cpu",
          "--synthetic", "--preset", "cpu-small", "--epochs", "2",
          "--nodes", "24", "-cpt", "3", "1", "1",
          "-date", "0101", "0109", "0110", "0112",
