@@ -322,8 +322,10 @@ at::Tensor spmm_axpby(at::Tensor xin, c10::optional<at::Tensor> p1,
 }
 
 // ---------------------------------------------------------------------------
-// Fused LSTM: forward kernel + dgrad kernel; weight grads
-// are computed on the python side as plain library GEMMs over the dA stream.
+// Fused LSTM: forward kernel + dgrad kernel + one batched
+// wgrad kernel over the dA stream. lstm_bwd returns dA with logical shape
+// (L, Tst, S_pad, 4H) but each 32-row sequence tile stored in the wgrad MFMA
+// fragment order documented in csrc/common.h; lstm_wgrad expects that order.
 
 extern "C" void stmgcn_lstm_fwd(void* stream, int dtype, const void* x,
                                 void* out, void* hseq_g, void* cseq_g,
@@ -351,7 +353,7 @@ extern "C" void stmgcn_atb_wgrad_multi(void* stream, int dtype,
                                        const void* B, float* C, float* db,
                                        long rows, int N);
 
-static constexpr int kSeqTile = 32;  // MUST match SEQ_TILE in fused_rnn.hip
+static constexpr int kSeqTile = 32;  // MUST match SEQ_TILE in common.h
 static constexpr int kH = 64;
 
 std::vector<at::Tensor> lstm_fwd(at::Tensor x, std::vector<at::Tensor> w_ih,
@@ -432,7 +434,7 @@ std::vector<at::Tensor> lstm_bwd(at::Tensor dout, at::Tensor x,
   return {dx, dA};
 }
 
-// All-layer LSTM weight grads in ONE launch over the dA stream (wgrad.hip):
+// All-layer LSTM weight grads in ONE launch over the TILED dA stream (wgrad.hip):
 // returns fp32 (dwih (L,4H,64), dwhh (L,4H,H), db (L,4H)); layer 0's live
 // dwih columns are [:, :cin].
 std::vector<at::Tensor> lstm_wgrad(at::Tensor dA, at::Tensor hseq, at::Tensor x) {
@@ -443,6 +445,10 @@ std::vector<at::Tensor> lstm_wgrad(at::Tensor dA, at::Tensor hseq, at::Tensor x)
   const long R = (long)Tst * S_pad;
   const int S = x.size(0), cin = x.size(2);
   TORCH_CHECK(cin == 1 || cin == kH);
+  TORCH_CHECK(dA.size(3) == 4 * kH && S_pad % kSeqTile == 0 && S <= S_pad,
+              "dA must be (L, Tst, S_pad, 4H) with S_pad a multiple of 32");
+  TORCH_CHECK(hseq.dim() == 4 && hseq.size(0) == L && hseq.size(1) == Tst &&
+              hseq.size(2) == S_pad && hseq.size(3) == kH && x.size(1) == Tst);
   auto fopt = dA.options().dtype(at::kFloat);
   // one fill for all three atomic-accumulated outputs
   const long n_w = (long)L * 4 * kH * kH;

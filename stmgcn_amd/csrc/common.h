@@ -45,7 +45,48 @@ __device__ __forceinline__ int lds_swz(int s, int cbyte) {
   return s * 128 + (cbyte ^ ((((unsigned)s >> 1) & 7) << 4));
 }
 
-#define STM_CHECK_HIP(expr)                                                     \
+// ---------------------------------------------------------------------------
+// dA stream layout (lstm_bwd -> lstm_wgrad hand-off).
+//
+// The gate-preactivation gradient tensor keeps its logical shape
+// (L, Tst, S_pad, 4H) and size, but inside every 32-row sequence tile the
+// elements are stored in the wgrad MFMA A-fragment order instead of row-major:
+//
+//   tile (l, t, b = s / 32) starts at element ((l*Tst + t)*S_pad + 32b) * 4H
+//   and holds [gate g = 0..4H-1][k' = 0..31] (k' contiguous, 64 B per gate);
+//   element (g, k') is dA[row 32b + rho(k')][g] with
+//     rho(k') = 16*((k'>>2)&1) + 4*(k'>>3) + (k'&3)
+//   i.e. k' = 8*lgrp + 4*m + r  <->  row = 16*m + 4*lgrp + r, which is the
+//   MFMA D-fragment ownership of the pointwise phase of lstm_bwd_kernel: a
+//   lane's 8 values per (gate slot, channel) are 8 consecutive k' = one 16 B
+//   store, and the wgrad lane (l16, lgrp) of gate g loads its A-fragment as
+//   the 16 B at k' = 8*lgrp. The permutation rho of the reduction index is
+//   free as long as the B operand (h_{t-1} / layer input rows) uses it too.
+#define SEQ_TILE 32   // sequences per RNN workgroup tile == dA tile rows
+#define STM_DA_GATES 256                          // 4H, H = 64
+#define STM_DA_TILE_ELEMS (SEQ_TILE * STM_DA_GATES)
+static_assert(SEQ_TILE == 32, "dA tile layout (rho) is defined for 32-row tiles");
+
+// element offset of the tile whose first flat row (t*S_pad + s) is row0
+__host__ __device__ constexpr long stm_da_tile_off(long row0) {
+  return row0 * STM_DA_GATES;
+}
+// element offset of (gate g, reduction slot k') inside a tile
+__host__ __device__ constexpr int stm_da_elem(int g, int kp) {
+  return g * SEQ_TILE + kp;
+}
+// k' -> tile row, and its inverse
+__host__ __device__ constexpr int stm_da_rho(int kp) {
+  return 16 * ((kp >> 2) & 1) + 4 * (kp >> 3) + (kp & 3);
+}
+__host__ __device__ constexpr int stm_da_rho_inv(int row) {
+  return 8 * ((row >> 2) & 3) + 4 * (row >> 4) + (row & 3);
+}
+static_assert(stm_da_rho(0) == 0 && stm_da_rho(4) == 16 && stm_da_rho(8) == 4 &&
+              stm_da_rho(31) == 31 && stm_da_rho_inv(stm_da_rho(13)) == 13 &&
+              stm_da_rho_inv(stm_da_rho(22)) == 22, "rho / rho_inv mismatch");
+
+#define STM_CHECK_HIP(expr)                                                    \
   do {                                                                          \
     hipError_t _e = (expr);                                                     \
     if (_e != hipSuccess) {                                                     \

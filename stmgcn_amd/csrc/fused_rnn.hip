@@ -34,8 +34,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // 32-row sequence tiles: MT=2 m-tiles/wave halves per-wave register state
 // vs the original 64-row tiles (fwd was 230 VGPR + 68 AGPR -> occupancy 1
 // wave/SIMD; 32-row tiles fit 2 workgroups/CU, hiding LDS/MFMA latency).
-#define SEQ_TILE 32
+// SEQ_TILE (= 32) lives in common.h next to the dA tile layout it fixes.
 #define RNN_H 64
+static_assert(4 * RNN_H == STM_DA_GATES, "dA tile layout assumes 4H = 256");
 #define MAX_LAYERS 8
 #define MAX_T 16
 
@@ -421,9 +422,14 @@ extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
 // layout — then two MFMA GEMMs produce dh_{t-1} (recurrent carry, kept in
 // registers) and dx_t (written into the dh hand-off LDS slot for the layer
 // below, or to the dx output at layer 0). dA is also streamed to global in
-// natural (L,Tst,S_pad,4H) order; the weight gradients are then two plain
-// library GEMMs per layer on the host side (dW = dA^T @ [h_prev | x]),
-// which keeps this kernel lean (no long-lived dW accumulators).
+// the tiled wgrad-fragment order documented in common.h (each lane's 8
+// values per gate slot are one 16 B store straight from the pointwise
+// registers); lstm_wgrad_kernel (wgrad.hip) then forms all weight gradients
+// dW = dA^T @ [h_prev | x] in one launch, which keeps this kernel lean (no
+// long-lived dW accumulators).
+
+// dA stream store placement in lstm_bwd_kernel (see the pointwise phase)
+constexpr bool kDaStoreEarly = false;
 
 __device__ __forceinline__ int swzA(int s, int cbyte) {      // dA rows: 512 B
   return s * 512 + (cbyte ^ ((s & 15) << 4));
@@ -442,13 +448,14 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
                 const T* __restrict__ gates_g,
                 RnnPtrs w,                      // w_ih/w_hh = TRANSPOSED (C|H, 4H)
                 T* __restrict__ dx,             // (S,Tst,Cin)
-                T* __restrict__ dA_g,           // (L,Tst,S_pad,4H)
+                T* __restrict__ dA_g,           // (L,Tst,S_pad,4H) tiled
                 T* __restrict__ dh_g,           // (Tst,S_pad,H) layer hand-off
                                                 // scratch (null when L == 1)
                 int S, int Tst, int L, int ret_seq) {
   using frag = typename Frag8<T>::type;
   using elem = typename Frag8<T>::elem;
   constexpr int MT = ST / 16;
+  static_assert(ST == SEQ_TILE, "one workgroup emits exactly one dA tile per step");
   extern __shared__ char lds[];
   const int s0 = blockIdx.x * ST;
   const int wv = threadIdx.x >> 6;
@@ -542,6 +549,9 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
         for (int q = 0; q < 4; ++q) wih0[q] = toF<T>(WihT[q * 64 + hch]);
       }
       float dxpart[MT][4];
+      // this lane's dA values, packed in stream order: slot q, k' - 8*lgrp =
+      // 4*m + r (common.h) -> one 16 B piece per gate slot
+      alignas(16) T pk[4][MT * 4];
 
       #pragma unroll
       for (int m = 0; m < MT; ++m) {
@@ -592,13 +602,34 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
             dAg = dcv * i_ * (1.f - g_ * g_);
             dc[m][r] = dcv * f_;
           }
-          *(T*)&dA_lds[swzA(row, (0 * 64 + hch) * 2)] = fromF<T>(dAi);
-          *(T*)&dA_lds[swzA(row, (1 * 64 + hch) * 2)] = fromF<T>(dAf);
-          *(T*)&dA_lds[swzA(row, (2 * 64 + hch) * 2)] = fromF<T>(dAg);
-          *(T*)&dA_lds[swzA(row, (3 * 64 + hch) * 2)] = fromF<T>(dAo);
+          pk[0][4 * m + r] = fromF<T>(dAi);
+          pk[1][4 * m + r] = fromF<T>(dAf);
+          pk[2][4 * m + r] = fromF<T>(dAg);
+          pk[3][4 * m + r] = fromF<T>(dAo);
+          #pragma unroll
+          for (int q = 0; q < 4; ++q)
+            *(T*)&dA_lds[swzA(row, (q * 64 + hch) * 2)] = pk[q][4 * m + r];
           if (l0cin1)
             dxpart[m][r] = dAi * wih0[0] + dAf * wih0[1] + dAg * wih0[2] + dAo * wih0[3];
         }
+      }
+      // ---- dA stream for the wgrad kernel, tile order (common.h): the lane's
+      // 4 x 16 B pieces; a wave's store per gate slot covers 1 KiB contiguous.
+      // kDaStoreEarly: store straight from the pointwise registers, before
+      // the barrier. Measured ~1% slower than the end-of-stage store (the
+      // first weight-fragment wait of GEMM1 then also drains these stores —
+      // vmcnt retires in order — on the serial dh_prev path). Default: park
+      // the pieces in the lane-private gates slot, which is dead from here
+      // until the end-of-stage stage-in (exactly 64 B per lane), and store
+      // after the GEMMs, where the next drain is a whole pointwise phase away.
+      T* out_dA = dA_g + stm_da_tile_off(base * S_pad + s0);
+      #pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (kDaStoreEarly)
+          *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
+              *(const frag*)pk[q];
+        else
+          *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
       }
       __syncthreads();   // dA visible to all waves
 
@@ -632,8 +663,6 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       }
 
       // ---- GEMM1: dh_prev = dA @ W_hh ------------------------------------
-      // (the dA global stream moved below the GEMMs: dh_prev is the serial
-      // BPTT critical path, the stream stores fill the gaps after it)
       if (t > 0) {
         f32x4 acc[MT];
         #pragma unroll
@@ -705,14 +734,13 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
         }
       }
 
-      // ---- stream dA to global (natural layout) for the wgrad kernel -----
-      {
-        T* out_dA = dA_g + base * (S_pad * 4 * RNN_H) + (long)s0 * 4 * RNN_H;
-        for (int i = threadIdx.x; i < ST * 32; i += 256) {
-          const int c8 = i & 31, sA = i >> 5;   // 32 x 16B pieces per row
-          *(frag*)&out_dA[(long)sA * 4 * RNN_H + c8 * 8] =
-              *(const frag*)&dA_lds[swzA(sA, c8 * 16)];
-        }
+      // ---- stream the parked dA pieces to global (4 x ds_read_b128 of the
+      // lane's own slot; no cross-lane traffic, no barrier) ------------------
+      if (!kDaStoreEarly) {
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
+              *(const frag*)&gmine[q * 16];
       }
 
       if (t > 0) {
@@ -761,7 +789,7 @@ lstm_bwd_wave_kernel(const T* __restrict__ dout,    // (S,H) or (S,Tst,H)
                      const T* __restrict__ gates_g, // fwd save
                      RnnPtrs w,                     // w_ih/w_hh TRANSPOSED (C|H, 4H)
                      T* __restrict__ dx,            // (S,Tst,Cin)
-                     T* __restrict__ dA_g,          // (L,Tst,S_pad,4H) natural
+                     T* __restrict__ dA_g,          // (L,Tst,S_pad,4H) tiled
                      T* __restrict__ dh_g,          // (Tst*S_pad*H) packed scratch
                      int S, int S_pad, int Tst, int L, int ret_seq) {
   using frag = typename Frag8<T>::type;
@@ -839,8 +867,11 @@ lstm_bwd_wave_kernel(const T* __restrict__ dout,    // (S,H) or (S,Tst,H)
       // ---- pointwise in D-layout; dA transposed through wave LDS --------
       float dxacc[4];                              // [r] (CIN1 l0 only)
       if (l0cin1) { dxacc[0] = dxacc[1] = dxacc[2] = dxacc[3] = 0.f; }
+      T* out_dA = dA_g + stm_da_tile_off((lay_base + t) * (long)S_pad
+                                         + (long)bxf * SEQ_TILE);
       #pragma unroll 1
       for (int nt = 0; nt < 4; ++nt) {             // serialized: live-range cap
+        alignas(8) T pk[4][4];                     // [slot q][r] stream pieces
         frag gf0 = *(const frag*)&gmine[nt * 32 + 0];   // [i r0..3 | f r0..3]
         frag gf1 = *(const frag*)&gmine[nt * 32 + 16];  // [g r0..3 | o r0..3]
         #pragma unroll
@@ -888,14 +919,25 @@ lstm_bwd_wave_kernel(const T* __restrict__ dout,    // (S,H) or (S,Tst,H)
           }
           const int rl = 4 * lgrp + r;             // wave-local row
           const int ch = 16 * nt + l16;
-          *(T*)&dAw[swzA(rl, (0 * 64 + ch) * 2)] = fromF<T>(dAi);
-          *(T*)&dAw[swzA(rl, (1 * 64 + ch) * 2)] = fromF<T>(dAf);
-          *(T*)&dAw[swzA(rl, (2 * 64 + ch) * 2)] = fromF<T>(dAg);
-          *(T*)&dAw[swzA(rl, (3 * 64 + ch) * 2)] = fromF<T>(dAo);
+          pk[0][r] = fromF<T>(dAi);
+          pk[1][r] = fromF<T>(dAf);
+          pk[2][r] = fromF<T>(dAg);
+          pk[3][r] = fromF<T>(dAo);
+          #pragma unroll
+          for (int q = 0; q < 4; ++q)
+            *(T*)&dAw[swzA(rl, (q * 64 + ch) * 2)] = pk[q][r];
           if (l0cin1)
             dxacc[r] += dAi * wihv[0][nt] + dAf * wihv[1][nt]
                       + dAg * wihv[2][nt] + dAo * wihv[3][nt];
         }
+        // dA stream, tile order (common.h): this wave owns m-tile mf of
+        // tile bxf, so its 4 rows per (slot, channel) are k' = 8*lgrp +
+        // 4*mf + r -> one 8 B piece
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *(ulong1*)&out_dA[stm_da_elem(q * RNN_H + 16 * nt + l16,
+                                        8 * lgrp + 4 * mf)] =
+              *(const ulong1*)pk[q];
       }
       // wave-private transpose: in-order LDS, no cross-wave traffic — the
       // A-fragment reads below only need the implicit lgkmcnt waits (kept
@@ -977,15 +1019,6 @@ lstm_bwd_wave_kernel(const T* __restrict__ dout,    // (S,H) or (S,Tst,H)
           const int row = row0 + 4 * lgrp + r;
           if (l16 == 0 && row < S) dx[(long)row * Tst + t] = fromF<T>(v);
         }
-      }
-
-      // ---- dA stream to global (natural layout, from the A-fragments) ---
-      {
-        T* out_dA = dA_g + (lay_base + t) * ((long)S_pad * 4 * RNN_H)
-                    + (long)(row0 + l16) * 4 * RNN_H;
-        #pragma unroll
-        for (int kk = 0; kk < 8; ++kk)
-          *(frag*)&out_dA[kk * 32 + lgrp * 8] = a_at(kk);
       }
 
       // ---- stage-end: stage the prefetched gates into lane LDS, rotate --

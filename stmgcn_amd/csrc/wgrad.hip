@@ -14,13 +14,12 @@
 // one unsafeAtomicAdd(f32) per output element per workgroup at the end.
 // Bias grads (column sums) ride along in the staging pass for free.
 //
-// LSTM variant reads the natural-layout dA stream (L, Tst*S_pad, 4H) written
-// by lstm_bwd_kernel and does ALL layers in one launch (grid.y = L). The
-// h_{t-1} operand for dw_hh is hseq offset by -S_pad rows (zero for t == 0):
-// the host-side torch.cat shift this replaces was 1.9% of step time.
-// grid.z splits the 256 gate rows into 256/GT slices: GT=128 halves the
-// per-wave accumulator state (full-GT compiled to 126 VGPR + 140 AGPR ->
-// 1 wave/SIMD; measured flat ~400 us across chunk counts = latency-bound).
+// LSTM variant reads the dA stream (L, Tst*S_pad, 4H) that lstm_bwd_kernel
+// writes in wgrad A-fragment tile order (common.h) — dA goes global ->
+// registers -> MFMA, only the hseq operands are transposed through LDS — and
+// does ALL layers in one launch (grid.y = L). The h_{t-1} operand for dw_hh
+// is hseq offset by -S_pad rows (zero for t == 0): the host-side torch.cat
+// shift this replaces was 1.9% of step time.
 
 #include "common.h"
 
@@ -98,203 +97,216 @@ __device__ __forceinline__ typename WFrag8<T>::type frag_from(
 }  // namespace
 
 // ===========================================================================
-// Fused multi-layer LSTM weight gradients: one launch, grid (nchunks, L).
+// Fused multi-layer LSTM weight gradients: one launch, grid (nchunks, L, 256/GT).
 //   dwih[l] += dA_l^T @ (l == 0 ? x : hseq[l-1])      (4H, cin_l<=64)
 //   dwhh[l] += dA_l^T @ hseq[l] shifted one step back (4H, H)
 //   db[l]   += colsum(dA_l)                           (4H,)
-// dA: (L, R=Tst*S_pad, 4H) natural; hseq: (L, R, H); x: (S, Tst, Cin).
-// Row r of the flat reduction dim maps to (t = r / S_pad, s = r % S_pad).
-// L0CIN1 instantiation covers ONLY layer 0 of the scalar-input (C_in == 1)
-// model: its dw_ih is a single column -> acc_ih collapses to one n-tile,
-// which keeps the unified register count at 2 waves/SIMD (the combined
-// variant compiled to 268 regs -> occupancy 1). layer = blockIdx.y + lbase.
+// dA: (L, R=Tst*S_pad, 4H) in the TILED order of common.h; hseq: (L, R, H)
+// natural; x: (S, Tst, Cin). Row r of the flat reduction dim maps to
+// (t = r / S_pad, s = r % S_pad); R is a whole number of 32-row tiles.
+//
+// dA is already stored as MFMA A-fragments: lane (l16, lgrp) of gate g reads
+// the 16 B at k' = 8*lgrp of the tile (a wave-load is 1 KiB contiguous),
+// global -> registers with no LDS and no barrier. Only the B operands (hp =
+// h_{t-1}, hx = layer input) go through LDS, transposed with their rows
+// placed at k' = rho^-1(row) so both operands agree on the reduction order.
+// Those two 8 KiB tiles per 64-row K-step are double-buffered: one barrier
+// per K-step (the commit of step k+2 into the buffer step k read is ordered
+// behind barrier k+1, which every wave reaches only after its step-k MFMAs).
+// db is the fp32 sum of each A-fragment's 8 values, reduced across lgrp by
+// two shuffles at the end.
+//
+// Every wave owns 32 gate rows (2 m-tiles); GT = gate rows per workgroup:
+// GT = 256 (512 threads) consumes whole dA rows per workgroup so hp/hx are
+// staged ONCE; GT = 128 (256 threads, grid.z = 2) re-reads them per slice.
+// The generic instantiation serves every layer in ONE launch (cin1 != 0:
+// layer 0 reads the scalar input x and only column 0 of its dw_ih is live).
+// The L0CIN1 instantiation covers ONLY layer 0 of that scalar-input model
+// with acc_ih collapsed to one n-tile, for the split two-launch variant
+// (STMGCN_WGRAD_SPLIT_L0=1). layer = blockIdx.y + lbase. Chunks are whole
+// tiles (tpc per workgroup); an odd tile count leaves the second half of the
+// last K-step zero.
 template <typename T, bool L0CIN1, int GT>
-__global__ void __launch_bounds__(256, 1)
+__global__ void __launch_bounds__(GT * 2, 1)
 lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
                   const T* __restrict__ x, float* __restrict__ dwih,
                   float* __restrict__ dwhh, float* __restrict__ db,
-                  long R, long S_pad, int S, int Tst, int L, int lbase) {
+                  long R, long S_pad, int S, int Tst, int L, int lbase,
+                  int cin1, long tpc) {
   using frag = typename WFrag8<T>::type;
-  constexpr int KT = 64;            // K-tile rows (PMC: 32-row tiles left the
-                                    // waves 65% parked on load latency —
-                                    // 2 MFMAs per frag per barrier now)
-  constexpr int MTG = GT / 64;      // gate m-tiles per wave (GT=128 -> 2)
-  constexpr int GU = (GT / 8) * (KT / 2);  // dA staging units per K-tile
-  extern __shared__ char lds[];
-  char* dAT = lds;                        // [GT][KT] T
-  char* hpT = lds + GT * 2 * KT;          // [64][KT] T
-  char* hxT = hpT + 64 * 2 * KT;          // [64][KT] T
-  float* red = (float*)lds;               // db reduction scratch (reuses dAT)
+  constexpr int NTHR = GT * 2;      // one wave per 32 gate rows
+  constexpr int MTG = 2;            // gate m-tiles per wave
+  constexpr int KT = 64;            // K-step rows = two dA tiles
+  constexpr int UPT = 512 / NTHR;   // hp/hx staging units per thread per K-step
+  constexpr int HT = 64 * 2 * KT;   // one transposed [64][KT] tile, bytes
+  static_assert(GT == 128 || GT == 256, "staging map covers 256/512 threads");
+  extern __shared__ char lds[];     // 2 x (hpT | hxT)
 
   const int layer = blockIdx.y + lbase;
-  const int g0 = blockIdx.z * GT;      // gate-row slice of this WG
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l16 = lane & 15, lgrp = lane >> 4;
-  const long chunk = (R + gridDim.x - 1) / gridDim.x;
-  const long r0 = (long)blockIdx.x * chunk;
-  const long r1 = (r0 + chunk < R) ? r0 + chunk : R;
+  const int gw = blockIdx.z * GT + wv * 32;   // this wave's first gate row
+  const long ntile = R / SEQ_TILE;
+  const long tb0 = (long)blockIdx.x * tpc;
+  const long tb1 = (tb0 + tpc < ntile) ? tb0 + tpc : ntile;
+  const long tp0 = S_pad / SEQ_TILE;          // tiles of t == 0 (no h_{t-1})
+  if (tb0 >= tb1) return;
 
-  const T* dA_l = dA + (long)layer * R * 256;
+  const T* dA_l = dA + (long)layer * R * STM_DA_GATES;
   const T* hp_l = hseq + (long)layer * R * 64;       // index r - S_pad
   const T* hx_l = (layer > 0) ? hseq + (long)(layer - 1) * R * 64 : nullptr;
   const bool l0 = L0CIN1 || (layer == 0);
+  const bool x1 = L0CIN1 || (cin1 && layer == 0);   // scalar layer-0 input
   constexpr int IHNT = L0CIN1 ? 1 : 4;   // dw_ih n-tiles
 
   f32x4 acc_hh[MTG][4], acc_ih[MTG][IHNT];
+  float dbp[MTG];
   #pragma unroll
   for (int mt = 0; mt < MTG; ++mt) {
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc_hh[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     #pragma unroll
     for (int nt = 0; nt < IHNT; ++nt) acc_ih[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dbp[mt] = 0.f;
   }
-  float dbp[GU / 256][8];
-  #pragma unroll
-  for (int s_ = 0; s_ < GU / 256; ++s_)
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) dbp[s_][j] = 0.f;
 
-  // Software-pipelined main loop: global loads for tile k+1 issue right
-  // after the barrier, overlapping tile k's MFMA phase.
-  static_assert(GU == 512, "two dA units per thread assumed by the pipeline");
-  const int pr = threadIdx.x & 31, cb = threadIdx.x >> 5;   // dA unit 0 (of 2)
-  const int pr2 = pr, cb2 = cb + 8;                         // dA unit 1
-  const int hcb = cb;                                       // hp/hx unit (8 blocks)
-  const bool hthread = true;  // all 256 threads carry one hp+hx unit
+  // hp/hx staging unit (512 per K-step: 2 operands x 32 row pairs x 8 column
+  // blocks): row pair p sits at k' = 2p, 2p+1 of K-half p >> 4, i.e. tile
+  // rows rho(2(p&15)) and the next one (rho keeps even/odd k' pairs adjacent).
+  // 8 consecutive lanes take the 8 column blocks of one row: 128 B coalesced.
+  const int scb = threadIdx.x & 7, sp = (threadIdx.x >> 3) & 31;
+  const int skh = sp >> 4, srow = stm_da_rho(2 * (sp & 15));
+  auto unit_op = [&](int u) { return (int)((threadIdx.x + u * NTHR) >> 8); };
 
-  frag va[2][2], vh[2], vx[2];     // [unit][row-pair half] / [row-pair half]
-  auto load_tiles = [&](long kt, frag a[2][2], frag h[2], frag xf[2]) {
+  auto load_h = [&](long tb, frag v[UPT][2]) {
     const frag fz = {};
-    const long ra = kt + pr * 2, rb = ra + 1;
+    const long tile = tb + skh;
+    const long r = tile * SEQ_TILE + srow;     // rows r, r + 1 (same tile)
     #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int cbu = (u == 0) ? cb : cb2;
-      a[u][0] = fz; a[u][1] = fz;
-      if (ra < r1) a[u][0] = *(const frag*)&dA_l[ra * 256 + g0 + cbu * 8];
-      if (rb < r1) a[u][1] = *(const frag*)&dA_l[rb * 256 + g0 + cbu * 8];
-    }
-    h[0] = fz; h[1] = fz; xf[0] = fz; xf[1] = fz;
-    // h_{t-1}: hseq[l] offset -S_pad rows, zero for t==0 (the guard must
-    // gate the LOAD — for layer 0, r - S_pad points before the allocation)
-    if (ra < r1 && ra >= S_pad)
-      h[0] = *(const frag*)&hp_l[(ra - S_pad) * 64 + hcb * 8];
-    if (rb < r1 && rb >= S_pad)
-      h[1] = *(const frag*)&hp_l[(rb - S_pad) * 64 + hcb * 8];
-    if (!l0) {
-      if (ra < r1) xf[0] = *(const frag*)&hx_l[ra * 64 + hcb * 8];
-      if (rb < r1) xf[1] = *(const frag*)&hx_l[rb * 64 + hcb * 8];
-    } else if (L0CIN1) {
-      if (hcb == 0) {
-        const long sa = ra % S_pad, ta = ra / S_pad;
-        const long sb = rb % S_pad, tb = rb / S_pad;
-        if (ra < r1 && sa < S) ((T*)&xf[0])[0] = x[sa * Tst + ta];
-        if (rb < r1 && sb < S) ((T*)&xf[1])[0] = x[sb * Tst + tb];
-      }
-    } else {
-      if (ra < r1) {
-        const long s_ = ra % S_pad, t_ = ra / S_pad;
-        if (s_ < S) xf[0] = *(const frag*)&x[(s_ * Tst + t_) * 64 + hcb * 8];
-      }
-      if (rb < r1) {
-        const long s_ = rb % S_pad, t_ = rb / S_pad;
-        if (s_ < S) xf[1] = *(const frag*)&x[(s_ * Tst + t_) * 64 + hcb * 8];
+    for (int u = 0; u < UPT; ++u) {
+      v[u][0] = fz; v[u][1] = fz;
+      if (tile >= tb1) continue;
+      if (unit_op(u) == 0) {
+        // h_{t-1}: hseq[l] offset -S_pad rows, zero for t==0 (the guard must
+        // gate the LOAD — for layer 0, r - S_pad points before the allocation)
+        if (tile >= tp0) {
+          v[u][0] = *(const frag*)&hp_l[(r - S_pad) * 64 + scb * 8];
+          v[u][1] = *(const frag*)&hp_l[(r + 1 - S_pad) * 64 + scb * 8];
+        }
+      } else if (!l0) {
+        v[u][0] = *(const frag*)&hx_l[r * 64 + scb * 8];
+        v[u][1] = *(const frag*)&hx_l[(r + 1) * 64 + scb * 8];
+      } else {
+        const long s_ = r % S_pad, t_ = r / S_pad;   // pad rows (s >= S) stay 0
+        if (x1) {
+          if (scb == 0) {
+            if (s_ < S) ((T*)&v[u][0])[0] = x[s_ * Tst + t_];
+            if (s_ + 1 < S) ((T*)&v[u][1])[0] = x[(s_ + 1) * Tst + t_];
+          }
+        } else {
+          if (s_ < S) v[u][0] = *(const frag*)&x[(s_ * Tst + t_) * 64 + scb * 8];
+          if (s_ + 1 < S)
+            v[u][1] = *(const frag*)&x[((s_ + 1) * Tst + t_) * 64 + scb * 8];
+        }
       }
     }
   };
-  auto commit_tiles = [&]() {
+  auto commit_h = [&](char* buf, const frag v[UPT][2]) {
     #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int cbu = (u == 0) ? cb : cb2;
+    for (int u = 0; u < UPT; ++u) {
+      char* tileT = buf + unit_op(u) * HT;
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
         union { T t2[2]; int i; } pk;
-        pk.t2[0] = ((const T*)&va[u][0])[j];
-        pk.t2[1] = ((const T*)&va[u][1])[j];
-        *(int*)&dAT[tswz64(cbu * 8 + j, pr * 4)] = pk.i;
-        dbp[u][j] += toF<T>(pk.t2[0]) + toF<T>(pk.t2[1]);
+        pk.t2[0] = ((const T*)&v[u][0])[j];
+        pk.t2[1] = ((const T*)&v[u][1])[j];
+        *(int*)&tileT[tswz64(scb * 8 + j, sp * 4)] = pk.i;
       }
     }
+  };
+  // dA A-fragments of one K-step: [K-half = tile][m-tile]
+  auto load_a = [&](long tb, frag a[2][MTG]) {
+    const frag fz = {};
     #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      union { T t2[2]; int i; } pk;
-      pk.t2[0] = ((const T*)&vh[0])[j];
-      pk.t2[1] = ((const T*)&vh[1])[j];
-      *(int*)&hpT[tswz64(hcb * 8 + j, pr * 4)] = pk.i;
-      pk.t2[0] = ((const T*)&vx[0])[j];
-      pk.t2[1] = ((const T*)&vx[1])[j];
-      *(int*)&hxT[tswz64(hcb * 8 + j, pr * 4)] = pk.i;
-    }
+    for (int kh = 0; kh < 2; ++kh)
+      #pragma unroll
+      for (int mt = 0; mt < MTG; ++mt) {
+        a[kh][mt] = fz;
+        if (tb + kh < tb1)
+          a[kh][mt] = *(const frag*)&dA_l[stm_da_tile_off((tb + kh) * SEQ_TILE) +
+                                          stm_da_elem(gw + mt * 16 + l16, 8 * lgrp)];
+      }
   };
 
-  load_tiles(r0, va, vh, vx);
-  for (long kt = r0; kt < r1; kt += KT) {
-    commit_tiles();
+  // One K-step on register set (vs, a) and LDS buffer buf. The set is
+  // refilled for the step TWO ahead as soon as it has been consumed, so
+  // every load has a whole K-step in flight before its first use, and the
+  // two sets alternate by name (loop unrolled by 2): no register copies, so
+  // no wait on a load that was only just issued. Past the chunk end the
+  // loads issue nothing and leave zeros.
+  auto kstep = [&](long tb, char* buf, frag vs[UPT][2], frag a[2][MTG]) {
+    char* hpT = buf;
+    char* hxT = buf + HT;
+    commit_h(buf, vs);
+    load_h(tb + 4, vs);
     __syncthreads();
-    frag na[2][2], nh[2], nx[2];
-    const bool more = kt + KT < r1;
-    if (more) load_tiles(kt + KT, na, nh, nx);
-
-    // ---- MFMA: wave wv owns gate rows g0 + [wv*16*MTG, ...); two K-halves
     #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
       const int koff = kh * KT + lgrp * 16;   // byte offset of the K half
+      frag bh[4], bx[IHNT];
+      #pragma unroll
+      for (int nt = 0; nt < 4; ++nt) bh[nt] = frag_from64<T>(hpT, nt * 16 + l16, koff);
+      #pragma unroll
+      for (int nt = 0; nt < IHNT; ++nt) bx[nt] = frag_from64<T>(hxT, nt * 16 + l16, koff);
       #pragma unroll
       for (int mt = 0; mt < MTG; ++mt) {
-        const frag a = frag_from64<T>(dAT, wv * 16 * MTG + mt * 16 + l16, koff);
+        const frag af = a[kh][mt];
         #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
-          acc_hh[mt][nt] = wmfma(a, frag_from64<T>(hpT, nt * 16 + l16, koff),
-                                 acc_hh[mt][nt]);
+          acc_hh[mt][nt] = wmfma(af, bh[nt], acc_hh[mt][nt]);
         #pragma unroll
         for (int nt = 0; nt < IHNT; ++nt)
-          acc_ih[mt][nt] = wmfma(a, frag_from64<T>(hxT, nt * 16 + l16, koff),
-                                 acc_ih[mt][nt]);
+          acc_ih[mt][nt] = wmfma(af, bx[nt], acc_ih[mt][nt]);
+        float sa = 0.f;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) sa += (float)af[j];
+        dbp[mt] += sa;
       }
     }
-    __syncthreads();  // WAR: next commit overwrites the tiles
-    if (more) {
-      #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        va[u][0] = na[u][0]; va[u][1] = na[u][1];
-      }
-      vh[0] = nh[0]; vh[1] = nh[1]; vx[0] = nx[0]; vx[1] = nx[1];
-    }
+    load_a(tb + 4, a);
+  };
+
+  frag vs0[UPT][2], vs1[UPT][2], a0[2][MTG], a1[2][MTG];
+  load_h(tb0, vs0);
+  load_a(tb0, a0);
+  load_h(tb0 + 2, vs1);
+  load_a(tb0 + 2, a1);
+  for (long tb = tb0; tb < tb1; tb += 4) {
+    kstep(tb, lds, vs0, a0);
+    if (tb + 2 < tb1) kstep(tb + 2, lds + 2 * HT, vs1, a1);   // WG-uniform
   }
+
 
   // ---- writeback: one f32 atomic per output element per workgroup --------
   float* whh = dwhh + (long)layer * 256 * 64;
   float* wih = dwih + (long)layer * 256 * 64;
   #pragma unroll
-  for (int mt = 0; mt < MTG; ++mt)
+  for (int mt = 0; mt < MTG; ++mt) {
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
       #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        const int m = g0 + wv * 16 * MTG + mt * 16 + lgrp * 4 + rr;
+        const int m = gw + mt * 16 + lgrp * 4 + rr;
         const int n = nt * 16 + l16;
         unsafeAtomicAdd(&whh[m * 64 + n], acc_hh[mt][nt][rr]);
-        if (nt < IHNT)
+        if (nt < IHNT && (!x1 || n == 0))   // scalar input: one live column
           unsafeAtomicAdd(&wih[m * 64 + n], acc_ih[mt][nt < IHNT ? nt : 0][rr]);
       }
-
-  // ---- db: LDS cross-thread reduction, then atomics ----------------------
-  // unit u of thread tid covered gate block (tid>>5) + 8u, rows pr = tid&31
-  __syncthreads();      // all MFMA reads of dAT done before red reuses it
-  #pragma unroll
-  for (int u = 0; u < 2; ++u)
-    #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      red[(u * 256 + threadIdx.x) * 8 + j] = dbp[u][j];
-  __syncthreads();
-  if (threadIdx.x < GT) {
-    const int g = threadIdx.x;             // local gate within the slice
-    const int gb = g >> 3, j = g & 7;      // staging col-block of gate g
-    // contributors: 32 threads tid = (gb & 7) * 32 + pr, unit set gb >> 3
-    const int set = gb >> 3, base = (gb & 7) * 32;
-    float v = 0.f;
-    #pragma unroll
-    for (int k = 0; k < 32; ++k) v += red[(set * 256 + base + k) * 8 + j];
-    unsafeAtomicAdd(&db[layer * 256 + g0 + g], v);
+    // db: lane (l16, lgrp) holds the k' = 8*lgrp..+8 partial of gate l16
+    float v = dbp[mt];
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    if (lgrp == 0) unsafeAtomicAdd(&db[layer * 256 + gw + mt * 16 + l16], v);
   }
 }
 
@@ -303,40 +315,60 @@ extern "C" void stmgcn_lstm_wgrad(void* stream_v, int dtype, const void* dA,
                                   float* dwhh, float* db, long R, long S_pad,
                                   int S, int Tst, int L, int cin) {
   static long env_chunks = -1;   // STMGCN_WGRAD_CHUNKS: perf experiments
+  static int env_gt = -1;        // STMGCN_WGRAD_GT=128: gate-split variant
+  static int env_split = 0;      // STMGCN_WGRAD_SPLIT_L0=1: own launch for
+                                 // the scalar-input layer 0
   if (env_chunks < 0) {
     const char* e = getenv("STMGCN_WGRAD_CHUNKS");
     env_chunks = e ? atol(e) : 0;
+    const char* g = getenv("STMGCN_WGRAD_GT");
+    env_gt = (g && atoi(g) == 128) ? 128 : 256;
+    const char* sp = getenv("STMGCN_WGRAD_SPLIT_L0");
+    env_split = sp ? atoi(sp) : 0;
   }
-  constexpr int GT = 128;           // gate-slice width (grid.z = 256/GT)
+  if (R <= 0 || R % SEQ_TILE != 0) {
+    printf("stmgcn_lstm_wgrad: R=%ld is not a whole number of dA tiles\n", R);
+    return;
+  }
+  // chunks are whole 32-row tiles of the tiled dA stream
+  const long ntile = R / SEQ_TILE;
   const long target = env_chunks > 0 ? env_chunks : 512 / (L > 0 ? L : 1);
   long nchunks = (R + 1023) / 1024;
   if (nchunks > target) nchunks = target;
   if (nchunks < 1) nchunks = 1;
-  const size_t lds = (size_t)GT * 128 + 8192 + 8192;  // 64-row tiles
+  const long tpc = (ntile + nchunks - 1) / nchunks;   // tiles per workgroup
+  nchunks = (ntile + tpc - 1) / tpc;
+  const size_t lds = 2 * 2 * 8192;   // double-buffered hpT | hxT, 64-row steps
   hipStream_t stream = (hipStream_t)stream_v;
-  const dim3 blk(256);
-  auto launch = [&](auto tptr) {
+  auto launch = [&](auto tptr, auto gtc) {
     using TT = std::remove_pointer_t<decltype(tptr)>;
-    if (cin == 1) {
+    constexpr int GT = decltype(gtc)::value;   // gate rows per workgroup
+    const dim3 blk(GT * 2);
+    if (cin == 1 && env_split) {
       // layer 0 (single ih column) and layers >= 1 as separate instantiations
       hipLaunchKernelGGL((lstm_wgrad_kernel<TT, true, GT>),
                          dim3((unsigned)nchunks, 1, 256 / GT), blk, lds, stream,
                          (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0);
+                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, 1, tpc);
       if (L > 1)
         hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT>),
                            dim3((unsigned)nchunks, L - 1, 256 / GT), blk, lds,
                            stream, (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                           dwih, dwhh, db, R, S_pad, S, Tst, L, 1);
+                           dwih, dwhh, db, R, S_pad, S, Tst, L, 1, 0, tpc);
     } else {
       hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT>),
                          dim3((unsigned)nchunks, L, 256 / GT), blk, lds, stream,
                          (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0);
+                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, cin == 1 ? 1 : 0,
+                         tpc);
     }
   };
-  if (dtype == STM_BF16) launch((__hip_bfloat16*)nullptr);
-  else if (dtype == STM_F16) launch((__half*)nullptr);
+  auto by_gt = [&](auto tptr) {
+    if (env_gt == 128) launch(tptr, std::integral_constant<int, 128>{});
+    else launch(tptr, std::integral_constant<int, 256>{});
+  };
+  if (dtype == STM_BF16) by_gt((__hip_bfloat16*)nullptr);
+  else if (dtype == STM_F16) by_gt((__half*)nullptr);
 }
 
 // ===========================================================================
