@@ -11,6 +11,9 @@ model -> trainer -> test), plus MI355X extensions:
   --synthetic    generate the synthetic dataset in-memory (the reference
                  expects ./data/data_dict.npz but ships no data)
   --dtype        fp32 | bf16 | fp16 compute dtype
+  --kernel-type / --K  graph-kernel family and order (override the preset);
+                 dual_random_walk = bidirectional diffusion for directed graphs
+  --directed     with --synthetic: asymmetric weighted random graphs
 
 Distributed: launch under torchrun (one process per GPU, RCCL); rank/world
 are read from the environment and the train split is block-sharded.
@@ -53,6 +56,14 @@ def main():
     p.add_argument("--batch-size", type=int, default=None)
     p.add_argument("--dtype", type=str, default=None, choices=sorted(DTYPES))
     p.add_argument("--sparse", action="store_true", help="CSR supports (HIP recurrence path)")
+    p.add_argument("--kernel-type", type=str, default=None,
+                   choices=["chebyshev", "localpool", "random_walk_diffusion",
+                            "dual_random_walk"],
+                   help="graph-kernel family (overrides the preset)")
+    p.add_argument("--K", type=int, default=None,
+                   help="polynomial / diffusion order (overrides the preset)")
+    p.add_argument("--directed", action="store_true",
+                   help="synthetic data: asymmetric weighted random graphs")
     p.add_argument("--model-dir", type=str, default="./output")
     p.add_argument("--metrics", type=str, default=None, help="JSONL metrics path")
     p.add_argument("--graph", action="store_true",
@@ -70,6 +81,10 @@ def main():
         cfg = cfg.replace(batch_size=args.batch_size)
     if args.dtype:
         cfg = cfg.replace(dtype=args.dtype)
+    if args.kernel_type:
+        cfg = cfg.replace(kernel_type=args.kernel_type)
+    if args.K is not None:
+        cfg = cfg.replace(cheby_K=args.K)
     if args.obs_len != [3, 1, 1] or args.preset == "reference":
         cfg = cfg.replace(obs_len=list(args.obs_len), seq_len=sum(args.obs_len))
 
@@ -89,7 +104,8 @@ def main():
     # ---- data (L1) ----
     data_in = DataInput(M_adj=cfg.m_graphs, data_dir=args.data, norm_opt=True)
     if args.synthetic or not os.path.exists(args.data):
-        raw = make_synthetic_dataset(n_nodes=cfg.n_nodes, m_graphs=cfg.m_graphs)
+        raw = make_synthetic_dataset(n_nodes=cfg.n_nodes, m_graphs=cfg.m_graphs,
+                                     directed=args.directed)
         data = data_in.load_dict(raw)
     else:
         data = data_in.load_data()

@@ -1,7 +1,7 @@
 """Standalone kernel microbenchmarks (GPU) — per-kernel wall time via HIP
 events, for tuning without running the whole model.
 
-Usage: python bench/kernel_micro.py [--kernel lstm_wgrad|atb_wgrad|lstm|all]
+Usage: python bench/kernel_micro.py [--kernel lstm_wgrad|atb_wgrad|lstm|dual_gconv|all]
 Prints one JSON line per measurement.
 """
 from __future__ import annotations
@@ -81,6 +81,46 @@ def bench_lstm(C):
     print(json.dumps({"kernel": "lstm_fwd_bwd_wgrad", "us": round(us, 1)}))
 
 
+def bench_dual_gconv(C):
+    """Fused dual random-walk gconv fwd+bwd at the bench-1024 gconv shape on
+    a directed graph, next to the fused chebyshev K=2 gconv on a graph of the
+    same nnz per row (the yardstick: 1 generator, 3 supports)."""
+    import numpy as np
+    from stmgcn_amd.data.synthetic import _random_sparse_directed_adj
+    from stmgcn_amd.graph import SupportGenerator
+    from stmgcn_amd.ops.hip_ops import ChebGconvFn
+    B, N, Cin, Cout, K = 32, 1024, 64, 64, 2
+    A = torch.from_numpy(_random_sparse_directed_adj(
+        N, 9, np.random.default_rng(0)))
+    dual = SupportGenerator("dual_random_walk", K).process_csr(A).to("cuda")
+    # chebyshev wants a symmetric adjacency: symmetrizing 4 out-edges + ring
+    # gives ~10 nnz per generator row, as 9 out-edges + ring do per direction
+    A2 = torch.from_numpy(_random_sparse_directed_adj(
+        N, 4, np.random.default_rng(1)))
+    cheb = SupportGenerator("chebyshev", K).process_csr(
+        torch.maximum(A2, A2.T)).to("cuda")
+    res = {}
+    for name, csr in (("dual_gconv", dual), ("cheb_gconv_k2", cheb)):
+        x = torch.randn(B, N, Cin, device="cuda", dtype=torch.bfloat16,
+                        requires_grad=True)
+        W = (torch.randn(csr.K_supports * Cin, Cout, device="cuda",
+                         dtype=torch.bfloat16) * 0.1).requires_grad_(True)
+        b = torch.zeros(Cout, device="cuda", dtype=torch.bfloat16,
+                        requires_grad=True)
+        dy = torch.randn(B, N, Cout, device="cuda", dtype=torch.bfloat16)
+
+        def step():
+            y = ChebGconvFn.apply(x, W, b, csr, "relu", True)
+            torch.autograd.grad(y, (x, W, b), dy)
+        res[name] = timeit(step, iters=300, warmup=30)
+        nnz = [csr.nnz] + ([csr.dual.nnz] if csr.dual is not None else [])
+        print(json.dumps({"kernel": name + "_fwd_bwd", "us": round(res[name], 1),
+                          "supports": csr.K_supports,
+                          "nnz_per_row": [round(z / N, 2) for z in nnz]}))
+    print(json.dumps({"kernel": "dual_over_cheb_ratio",
+                      "ratio": round(res["dual_gconv"] / res["cheb_gconv_k2"], 3)}))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--kernel", default="all")
@@ -93,6 +133,8 @@ def main():
         bench_atb(C)
     if args.kernel in ("lstm", "all"):
         bench_lstm(C)
+    if args.kernel in ("dual_gconv", "all"):
+        bench_dual_gconv(C)
 
 
 if __name__ == "__main__":

@@ -21,7 +21,9 @@ class STMGCNConfig:
     lstm_num_layers: int = 3
     gcn_hidden_dim: int = 64
     m_graphs: int = 3                # M static region graphs
-    kernel_type: str = "chebyshev"   # chebyshev | localpool | random_walk_diffusion
+    # chebyshev | localpool | random_walk_diffusion (reference quirk 3: unusable)
+    # | dual_random_walk (bidirectional diffusion, for directed graphs)
+    kernel_type: str = "chebyshev"
     cheby_K: int = 2
     rnn_cell: str = "lstm"           # lstm | gru  (gru for the deep variant)
     n_blocks: int = 1                # stacked ST-MGCN blocks (deep variant = 4)
@@ -58,12 +60,14 @@ class STMGCNConfig:
         NOTE: the rw-diffusion preprocessor actually emits K+1 supports
         (GCN.py:77-81), so that kernel type is unusable end-to-end in the
         reference; we replicate the contract and document it.
+        dual_random_walk -> 2K+1 as well, and its preprocessor does emit them:
+        [I, T_1..T_K(G_f), T_1..T_K(G_b)] over both transition matrices.
         """
         if self.kernel_type == "localpool":
             return 1
         if self.kernel_type == "chebyshev":
             return self.cheby_K + 1
-        if self.kernel_type == "random_walk_diffusion":
+        if self.kernel_type in ("random_walk_diffusion", "dual_random_walk"):
             return 2 * self.cheby_K + 1
         raise ValueError(f"unknown kernel_type {self.kernel_type!r}")
 

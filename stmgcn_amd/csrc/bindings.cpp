@@ -303,6 +303,160 @@ at::Tensor cheb_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W,
   return dX;
 }
 
+// ---------------------------------------------------------------------------
+// Dual random-walk diffusion gconv (dual_gconv.hip): 2K+1 supports
+// [I, T_1..T_K(G_f), T_1..T_K(G_b)], both generators advanced per launch.
+
+extern "C" void stmgcn_dual_fused_fwd_step(
+    void* stream, int dtype, const int* rpf, const int* cif, const float* vf,
+    const int* rpb, const int* cib, const float* vb, const void* xf,
+    const void* pf1, const void* xb, const void* pb1, const void* x0,
+    const void* W, const void* bias, void* pfout, void* pbout, float* yacc,
+    void* yout, int B, int N, int C, int Cout, int kofs_f, int kofs_b,
+    float alpha, float beta, int first, int act);
+extern "C" void stmgcn_dual_fused_bwd_step(
+    void* stream, int dtype, const int* rpf, const int* cif, const float* vf,
+    const int* rpb, const int* cib, const float* vb, const void* xf,
+    const void* pf1, const void* xb, const void* pb1, const void* dz,
+    const void* W, void* outf, void* outb, int B, int N, int C, int Cout,
+    int kofs_f, int kofs_b, float alpha, float beta, int final_step);
+
+namespace {
+
+struct CsrPtrs {
+  const int *rp, *ci;
+  const float* v;
+};
+
+CsrPtrs csr_ptrs(const at::Tensor& rowptr, const at::Tensor& colidx,
+                 const at::Tensor& vals, int N) {
+  TORCH_CHECK(rowptr.is_cuda() && colidx.is_cuda() && vals.is_cuda());
+  TORCH_CHECK(rowptr.scalar_type() == at::kInt && colidx.scalar_type() == at::kInt &&
+              vals.scalar_type() == at::kFloat);
+  TORCH_CHECK(rowptr.is_contiguous() && colidx.is_contiguous() && vals.is_contiguous());
+  TORCH_CHECK(rowptr.numel() == N + 1 && colidx.numel() == vals.numel());
+  return {rowptr.data_ptr<int>(), colidx.data_ptr<int>(), vals.data_ptr<float>()};
+}
+
+}  // namespace
+
+// y = act(x W_0 + sum_k (T_k(G_f) x) W_k + (T_k(G_b) x) W_{K+k} + b) in K
+// launches. training=true additionally returns pf_1..pf_K, pb_1..pb_K for the
+// wgrad; eval ping/pongs two buffers per direction.
+std::vector<at::Tensor> dual_gconv_fused_fwd(
+    at::Tensor x, at::Tensor rpf, at::Tensor cif, at::Tensor vf,
+    at::Tensor rpb, at::Tensor cib, at::Tensor vb, at::Tensor W,
+    c10::optional<at::Tensor> bias, int64_t K, int64_t act, bool training) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf,
+              "fused dual gconv serves bf16/f16");
+  TORCH_CHECK(W.is_contiguous() && W.scalar_type() == x.scalar_type());
+  const int B = x.size(0), N = x.size(1), C = x.size(2);
+  const int Cout = W.size(1);
+  TORCH_CHECK(K >= 1 && C <= 64 && Cout <= 64,
+              "fused dual gconv serves K >= 1, C/Cout <= 64");
+  TORCH_CHECK(W.size(0) == (2 * K + 1) * C);
+  const int dt = dtype_code(x);
+  void* st = stream();
+  const CsrPtrs gf = csr_ptrs(rpf, cif, vf, N), gb = csr_ptrs(rpb, cib, vb, N);
+  auto y = at::empty({B, N, Cout}, x.options());
+  at::Tensor bc;
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->scalar_type() == x.scalar_type() && bias->numel() == Cout);
+    bc = bias->contiguous();
+    bp = bc.data_ptr();
+  }
+  at::Tensor yacc;
+  float* ya = nullptr;
+  if (K > 1) {
+    yacc = at::empty({B, N, Cout}, x.options().dtype(at::kFloat));
+    ya = yacc.data_ptr<float>();
+  }
+  const int nbuf = training ? (int)K : std::min<int>(2, (int)K);
+  std::vector<at::Tensor> pf, pb;
+  for (int i = 0; i < nbuf; ++i) {
+    pf.push_back(at::empty({B, N, C}, x.options()));
+    pb.push_back(at::empty({B, N, C}, x.options()));
+  }
+  // k = 1: p_1 = G x (both directions); acc = x W_0 + pf_1 W_1 + pb_1 W_{K+1}
+  stmgcn_dual_fused_fwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
+                             x.data_ptr(), nullptr, x.data_ptr(), nullptr,
+                             x.data_ptr(), W.data_ptr(), bp, pf[0].data_ptr(),
+                             pb[0].data_ptr(), ya,
+                             K == 1 ? y.data_ptr() : nullptr, B, N, C, Cout,
+                             C, (int)(K + 1) * C, 1.f, 0.f, 1, (int)act);
+  // k >= 2: p_k = 2 G p_{k-1} - p_{k-2}; eval writes p_k over p_{k-2} from
+  // k = 3 on (never over x) — the p1 == pout aliasing the kernel allows
+  const void *f2 = x.data_ptr(), *b2 = x.data_ptr();
+  void *f1 = pf[0].data_ptr(), *b1 = pb[0].data_ptr();
+  for (int k = 2; k <= K; ++k) {
+    void* df = (training || k == 2) ? pf[k - 1].data_ptr() : const_cast<void*>(f2);
+    void* db = (training || k == 2) ? pb[k - 1].data_ptr() : const_cast<void*>(b2);
+    stmgcn_dual_fused_fwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
+                               f1, f2, b1, b2, nullptr, W.data_ptr(), bp, df,
+                               db, ya, k == K ? y.data_ptr() : nullptr, B, N,
+                               C, Cout, k * C, (int)(K + k) * C, 2.f, -1.f, 0,
+                               (int)act);
+    f2 = f1; f1 = df;
+    b2 = b1; b1 = db;
+  }
+  std::vector<at::Tensor> out{y};
+  if (training) {
+    out.insert(out.end(), pf.begin(), pf.end());
+    out.insert(out.end(), pb.begin(), pb.end());
+  }
+  return out;
+}
+
+// dX = U_0 + sum_k T_k(G_f)^T U_k + T_k(G_b)^T U_{K+k}, U_j = dz W_j^T, via
+// two Clenshaw chains over the transposed CSRs advanced together: K+1 launches.
+at::Tensor dual_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W, at::Tensor rpf_t,
+                                   at::Tensor cif_t, at::Tensor vf_t,
+                                   at::Tensor rpb_t, at::Tensor cib_t,
+                                   at::Tensor vb_t, int64_t K) {
+  TORCH_CHECK(dz.is_cuda() && dz.dim() == 3 && dz.is_contiguous());
+  TORCH_CHECK(dz.scalar_type() == at::kBFloat16 || dz.scalar_type() == at::kHalf,
+              "fused dual gconv serves bf16/f16");
+  TORCH_CHECK(W.is_contiguous() && W.scalar_type() == dz.scalar_type());
+  const int B = dz.size(0), N = dz.size(1), Cout = dz.size(2);
+  TORCH_CHECK(K >= 1 && W.size(0) % (2 * K + 1) == 0 && W.size(1) == Cout);
+  const int C = W.size(0) / (2 * K + 1);
+  TORCH_CHECK(C <= 64 && Cout <= 64);
+  const int dt = dtype_code(dz);
+  void* st = stream();
+  const CsrPtrs gf = csr_ptrs(rpf_t, cif_t, vf_t, N),
+                gb = csr_ptrs(rpb_t, cib_t, vb_t, N);
+  auto dX = at::empty({B, N, C}, dz.options());
+
+  auto bwd = [&](const void* xf, const void* pf1, const void* xb,
+                 const void* pb1, void* outf, void* outb, int j, float alpha,
+                 float beta) {
+    stmgcn_dual_fused_bwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
+                               xf, pf1, xb, pb1, dz.data_ptr(), W.data_ptr(),
+                               outf, outb, B, N, C, Cout, j * C,
+                               (int)(K + j) * C, alpha, beta, j == 0);
+  };
+  // b_K = U_K; b_j = U_j + 2 G^T b_{j+1} - b_{j+2}; dX = U_0 + sum over both
+  // chains of (G^T b_1 - b_2). Two ping/pong buffers per direction.
+  const int nbuf = K > 1 ? 2 : 1;
+  std::vector<at::Tensor> bufs;
+  for (int i = 0; i < 2 * nbuf; ++i)
+    bufs.push_back(at::empty({B, N, C}, dz.options()));
+  void *f1 = bufs[0].data_ptr(), *g1 = bufs[1].data_ptr();   // b_{j+1}
+  void *f2 = nullptr, *g2 = nullptr;                          // b_{j+2}
+  bwd(nullptr, nullptr, nullptr, nullptr, f1, g1, (int)K, 0.f, 0.f);
+  void* of = K > 1 ? bufs[2].data_ptr() : nullptr;
+  void* og = K > 1 ? bufs[3].data_ptr() : nullptr;
+  for (int j = (int)K - 1; j >= 1; --j) {
+    bwd(f1, f2, g1, g2, of, og, j, 2.f, f2 ? -1.f : 0.f);
+    f2 = f1; f1 = of; of = f2;   // overwritten next iteration (element-safe)
+    g2 = g1; g1 = og; og = g2;
+  }
+  bwd(f1, f2, g1, g2, dX.data_ptr(), nullptr, 0, 1.f, f2 ? -1.f : 0.f);
+  return dX;
+}
+
 // Plain axpby-SpMM on (B,N,C): out = alpha*(G @ xin) + beta*p1 — the
 // recurrence-replay primitive for the fused wgrad (backward recompute).
 at::Tensor spmm_axpby(at::Tensor xin, c10::optional<at::Tensor> p1,
@@ -740,6 +894,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused ChebConv fwd: recurrence + MFMA mix + bias + act, no stack");
   m.def("cheb_gconv_fused_bwd_dx", &cheb_gconv_fused_bwd_dx,
         "Fused ChebConv dX: Clenshaw over G^T with in-kernel U = dz W^T");
+  m.def("dual_gconv_fused_fwd", &dual_gconv_fused_fwd,
+        "Fused dual random-walk gconv fwd: both recurrences + mix per launch");
+  m.def("dual_gconv_fused_bwd_dx", &dual_gconv_fused_bwd_dx,
+        "Fused dual random-walk gconv dX: both Clenshaw chains per launch");
   m.def("spmm_axpby", &spmm_axpby,
         "out = alpha*(G @ xin) + beta*p1 on (B,N,C) (recurrence replay)");
   m.def("atb_wgrad_into", &atb_wgrad_into,

@@ -7,6 +7,10 @@ which materializes a dense (K_supports, N, N) stack offline:
               supports = Chebyshev polynomials T_0..T_K of L~      (GCN.py:66-75)
   localpool:  single support I + A_hat                             (GCN.py:68-70)
   random_walk_diffusion: supports = T_0..T_K of P^T, P = D^-1 A    (GCN.py:77-81)
+  dual_random_walk: [I, T_1..T_K(G_f), T_1..T_K(G_b)] with
+              G_f = (D_out^-1 A)^T, G_b = (D_in^-1 A^T)^T — the bidirectional
+              diffusion convolution for directed graphs (Li et al., ICLR'18);
+              no reference counterpart (its 2K+1 contract is never met there)
   recurrence: T_0 = I, T_1 = G, T_k = 2 G T_{k-1} - T_{k-2}        (GCN.py:125-135)
 
 The reference's torch.eig call raises on torch>=1.10, so lambda_max == 2 is
@@ -20,8 +24,9 @@ kernel; dense stacks remain available for parity tests and the CPU oracle.
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -77,6 +82,11 @@ class CSRSupport:
     kind == "cheby":  supports are T_0=I, T_1=G, T_k = 2 G T_{k-1} - T_{k-2},
                       K_s = K+1 of them (chebyshev & rw-diffusion families).
     kind == "single": one support, the matrix G itself (localpool).
+    kind == "dual":  2K+1 supports [I, T_1..T_K(G_f), T_1..T_K(G_b)] of the
+                      dual random-walk diffusion. This object's own arrays
+                      hold the forward generator G_f; ``dual`` holds a
+                      "cheby" CSRSupport (K+1 supports) of the backward
+                      generator G_b.
 
     Carries BOTH G and G^T in CSR: backward applies T_k(G)^T = T_k(G^T)
     (rw-diffusion's P^T is asymmetric; for the symmetric chebyshev/localpool
@@ -87,10 +97,11 @@ class CSRSupport:
     vals: torch.Tensor      # fp32  (nnz,)
     n_nodes: int
     K_supports: int
-    kind: str               # "cheby" | "single"
+    kind: str               # "cheby" | "single" | "dual"
     row_ptr_t: Optional[torch.Tensor] = None   # CSR of G^T
     col_idx_t: Optional[torch.Tensor] = None
     vals_t: Optional[torch.Tensor] = None
+    dual: Optional["CSRSupport"] = None        # kind == "dual": G_b
 
     def to(self, device) -> "CSRSupport":
         return CSRSupport(self.row_ptr.to(device), self.col_idx.to(device),
@@ -98,11 +109,20 @@ class CSRSupport:
                           self.kind,
                           None if self.row_ptr_t is None else self.row_ptr_t.to(device),
                           None if self.col_idx_t is None else self.col_idx_t.to(device),
-                          None if self.vals_t is None else self.vals_t.to(device))
+                          None if self.vals_t is None else self.vals_t.to(device),
+                          None if self.dual is None else self.dual.to(device))
 
     @property
     def nnz(self) -> int:
         return self.col_idx.numel()
+
+    def directions(self) -> Tuple["CSRSupport", "CSRSupport"]:
+        """kind == "dual" only: (forward, backward) as two "cheby" supports of
+        K+1 terms each, for code that runs one generator at a time."""
+        assert self.kind == "dual" and self.dual is not None
+        fwd = dataclasses.replace(self, K_supports=self.dual.K_supports,
+                                  kind="cheby", dual=None)
+        return fwd, self.dual
 
     def dense_generator(self) -> torch.Tensor:
         G = torch.zeros(self.n_nodes, self.n_nodes, dtype=self.vals.dtype)
@@ -113,6 +133,9 @@ class CSRSupport:
 
     def dense_supports(self) -> torch.Tensor:
         """Materialize the (K_s, N, N) stack — parity/oracle use only."""
+        if self.kind == "dual":
+            fwd, bwd = self.directions()
+            return torch.cat([fwd.dense_supports(), bwd.dense_supports()[1:]])
         G = self.dense_generator()
         if self.kind == "single":
             return G.unsqueeze(0)
@@ -150,6 +173,10 @@ def dense_to_csr(G: torch.Tensor, prune_eps: float = 0.0) -> CSRSupport:
     return CSRSupport(rp, ci, v, G.shape[0], 0, "", rpt, cit, vt)
 
 
+KERNEL_TYPES = ("chebyshev", "localpool", "random_walk_diffusion",
+                "dual_random_walk")
+
+
 class SupportGenerator:
     """MI355X-native replacement for the reference Adj_Preprocessor.
 
@@ -158,9 +185,9 @@ class SupportGenerator:
     """
 
     def __init__(self, kernel_type: str, K: int, lambda_max_mode: str = "fixed2"):
-        if kernel_type not in ("chebyshev", "localpool", "random_walk_diffusion"):
+        if kernel_type not in KERNEL_TYPES:
             raise ValueError(
-                "kernel_type must be one of [chebyshev, localpool, random_walk_diffusion]")
+                f"kernel_type must be one of [{', '.join(KERNEL_TYPES)}]")
         self.kernel_type = kernel_type
         # localpool ignores K (reference GCN.py:54)
         self.K = K if kernel_type != "localpool" else 1
@@ -185,12 +212,21 @@ class SupportGenerator:
             else:
                 raise ValueError(f"bad lambda_max_mode {self.lambda_max_mode!r}")
             return (2.0 / lmax) * L - torch.eye(L.shape[0])
-        # random_walk_diffusion: Chebyshev series of P^T (reference GCN.py:77-81)
+        # random_walk_diffusion: Chebyshev series of P^T (reference GCN.py:77-81);
+        # dual_random_walk: the same matrix is its forward generator G_f
         return random_walk_normalize(adj).T.contiguous()
+
+    def backward_generator(self, adj: torch.Tensor) -> torch.Tensor:
+        """dual_random_walk only: G_b = (D_in^-1 A^T)^T."""
+        return random_walk_normalize(adj.float().T).T.contiguous()
 
     # -- dense supports (parity surface) ------------------------------------
     def process(self, adj: torch.Tensor) -> torch.Tensor:
         G = self.generator(adj)
+        if self.kernel_type == "dual_random_walk":
+            Gb = self.backward_generator(adj)
+            return torch.stack(chebyshev_polynomials(G, self.K)
+                               + chebyshev_polynomials(Gb, self.K)[1:], dim=0)
         if self.kernel_type == "localpool":
             return G.unsqueeze(0)
         return torch.stack(chebyshev_polynomials(G, self.K), dim=0)
@@ -201,6 +237,10 @@ class SupportGenerator:
         csr = dense_to_csr(G, prune_eps)
         if self.kernel_type == "localpool":
             csr.K_supports, csr.kind = 1, "single"
+        elif self.kernel_type == "dual_random_walk":
+            csr.K_supports, csr.kind = 2 * self.K + 1, "dual"
+            csr.dual = dense_to_csr(self.backward_generator(adj), prune_eps)
+            csr.dual.K_supports, csr.dual.kind = self.K + 1, "cheby"
         else:
             csr.K_supports, csr.kind = self.K + 1, "cheby"
         return csr

@@ -208,13 +208,15 @@ class ST_MGCN(nn.Module):
     def get_support_K(config: dict) -> int:
         """Kernel config -> support count (reference STMGCN.py:80-91):
         localpool -> 1, chebyshev -> K+1, random_walk_diffusion -> 2K+1.
-        (rw-diffusion is unusable end-to-end in the reference — quirk 3.)"""
+        (rw-diffusion is unusable end-to-end in the reference — quirk 3.)
+        dual_random_walk -> 2K+1: identity plus K steps on each of the
+        forward and backward transition matrices (directed graphs)."""
         kt, K = config["kernel_type"], config.get("K", 2)
         if kt == "localpool":
             return 1
         if kt == "chebyshev":
             return K + 1
-        if kt == "random_walk_diffusion":
+        if kt in ("random_walk_diffusion", "dual_random_walk"):
             return 2 * K + 1
         raise ValueError(f"unknown kernel_type {kt!r}")
 

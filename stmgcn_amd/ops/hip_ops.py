@@ -1,7 +1,8 @@
 """autograd.Function wrappers over the CDNA4 HIP kernels (stmgcn_amd._C).
 
 Kernel coverage (all landed; SURVEY §2.4 op numbers in parentheses):
-  - ChebGconvFn (K1/K2/K10): fully fused ChebConv — in-kernel CSR support
+  - ChebGconvFn (K1/K2/K10; also the dual random-walk diffusion gconv over
+    two generators, dual_gconv.hip): fully fused ChebConv — in-kernel CSR support
     recurrence with the mix GEMM + bias + act as an MFMA epilogue of each
     step; backward = Clenshaw over G^T with the U = dz W^T GEMM fused
     in-kernel + one multi-source atb_wgrad launch for every dW_k.
@@ -70,6 +71,13 @@ class ChebGconvFn(torch.autograd.Function):
 
     Stack path (fp32 parity / larger widths): cheb_apply support stack +
     rocBLAS mix, Clenshaw combine backward.
+
+    csr.kind == "dual" (dual random-walk diffusion, 2K+1 supports
+    [I, T_k(G_f).., T_k(G_b)..]): the fused path (same dtype/width limits,
+    K <= 3) runs dual_gconv.hip — K forward launches and K+1 dX launches that
+    advance both generators together — and two atb_wgrad_multi launches
+    ([x, pf_1..pf_K] with db, then [pb_1..pb_K]). Its stack path runs
+    cheb_apply / cheb_combine once per generator.
     """
 
     @staticmethod
@@ -84,12 +92,27 @@ class ChebGconvFn(torch.autograd.Function):
         fused = (x.dtype in (torch.bfloat16, torch.float16)
                  and Cin <= 64 and Cout <= 64
                  and Cin % 8 == 0 and Cout % 8 == 0
-                 and csr.K_supports <= 4)   # atb_wgrad_multi: <= 4 sources
+                 # atb_wgrad_multi: <= 4 sources ([x, pf_1..pf_K] for dual)
+                 and (csr.K_supports <= 7 if csr.kind == "dual"
+                      else csr.K_supports <= 4))
         ctx.fused = fused
         ctx.csr = csr
         ctx.act = activation
         ctx.has_b = b is not None
         ctx.cin = Cin
+        if fused and csr.kind == "dual":
+            gb = csr.dual
+            outs = C.dual_gconv_fused_fwd(
+                x, csr.row_ptr, csr.col_idx, csr.vals,
+                gb.row_ptr, gb.col_idx, gb.vals, Wd,
+                b.to(x.dtype).contiguous() if b is not None else None,
+                gb.K_supports - 1, 1 if activation == "relu" else 0, training)
+            y = outs[0]
+            # outs[1:] = pf_1..pf_K, pb_1..pb_K
+            ctx.save_for_backward(x, Wd, W,
+                                  y if activation == "relu" else None,
+                                  *outs[1:])
+            return y
         if fused:
             outs = C.cheb_gconv_fused_fwd(
                 x, csr.row_ptr, csr.col_idx, csr.vals, Wd,
@@ -103,8 +126,14 @@ class ChebGconvFn(torch.autograd.Function):
                                   y if activation == "relu" else None,
                                   *outs[1:])
             return y
-        S = C.cheb_apply(x, csr.row_ptr, csr.col_idx, csr.vals,
-                         csr.K_supports, csr.kind == "single")
+        if csr.kind == "dual":
+            S = torch.cat(
+                [C.cheb_apply(x, g.row_ptr, g.col_idx, g.vals, g.K_supports,
+                              False)[:, :, skip:]
+                 for g, skip in zip(csr.directions(), (0, 1))], dim=2)
+        else:
+            S = C.cheb_apply(x, csr.row_ptr, csr.col_idx, csr.vals,
+                             csr.K_supports, csr.kind == "single")
         B_, N, K, _ = S.shape
         feat = S.view(B_, N, K * Cin)
         if b is not None:
@@ -131,6 +160,24 @@ class ChebGconvFn(torch.autograd.Function):
             single = csr.kind == "single"
             K_s = csr.K_supports
             Cin, Cout = ctx.cin, dz.shape[-1]
+            if csr.kind == "dual":
+                gb = csr.dual
+                K = gb.K_supports - 1
+                dX = C.dual_gconv_fused_bwd_dx(
+                    dz, Wd, csr.row_ptr_t, csr.col_idx_t, csr.vals_t,
+                    gb.row_ptr_t, gb.col_idx_t, gb.vals_t, K)
+                dWf = torch.zeros(K_s * Cin, Cout, dtype=torch.float32,
+                                  device=dz.device)
+                db_f = (torch.zeros(Cout, dtype=torch.float32,
+                                    device=dz.device) if ctx.has_b else None)
+                dz2 = dz.reshape(-1, Cout)
+                flat = [p.reshape(-1, Cin) for p in (x,) + tuple(ps)]
+                # rows [0,(K+1)Cin): x, pf_1..pf_K (+ db); rest: pb_1..pb_K
+                C.atb_wgrad_multi(flat[:K + 1], dz2, dWf[:(K + 1) * Cin], db_f)
+                C.atb_wgrad_multi(flat[K + 1:], dz2, dWf[(K + 1) * Cin:], None)
+                return (dX, dWf.to(W.dtype),
+                        db_f.to(W.dtype) if ctx.has_b else None,
+                        None, None, None)
             dX = C.cheb_gconv_fused_bwd_dx(dz, Wd, csr.row_ptr_t,
                                            csr.col_idx_t, csr.vals_t, K_s,
                                            single)
@@ -170,6 +217,16 @@ class ChebGconvFn(torch.autograd.Function):
             dW = (feat.reshape(-1, KC).T @ dz.reshape(-1, Cout)).to(W.dtype)
             db = dz.sum(dim=(0, 1)).to(W.dtype) if ctx.has_b else None
         U = (dz @ W.to(dz.dtype).T).view(B_, N, csr.K_supports, ctx.cin).contiguous()
+        if csr.kind == "dual":
+            # one Clenshaw per transpose; U_0 counts once (zeroed 2nd time)
+            gf, gb = csr.directions()
+            K1 = gf.K_supports
+            Ub = torch.cat([torch.zeros_like(U[:, :, :1]), U[:, :, K1:]], dim=2)
+            dX = (C.cheb_combine(U[:, :, :K1].contiguous(), gf.row_ptr_t,
+                                 gf.col_idx_t, gf.vals_t, False)
+                  + C.cheb_combine(Ub, gb.row_ptr_t, gb.col_idx_t, gb.vals_t,
+                                   False))
+            return dX, dW, db, None, None, None
         dX = C.cheb_combine(U, csr.row_ptr_t, csr.col_idx_t, csr.vals_t,
                             csr.kind == "single")
         return dX, dW, db, None, None, None

@@ -35,7 +35,12 @@ def gconv_mix_dense(A: torch.Tensor, x: torch.Tensor, W: torch.Tensor,
 def cheb_supports_apply(csr, x: torch.Tensor) -> torch.Tensor:
     """Support stack application via the sparse generator: returns
     (B, K_s, N, Cin) where slice k is T_k(G) @ x (oracle for the HIP
-    in-kernel recurrence)."""
+    in-kernel recurrence). kind == "dual": the 2K+1 slices
+    [x, T_1..T_K(G_f) x, T_1..T_K(G_b) x]."""
+    if csr.kind == "dual":
+        fwd, bwd = csr.directions()
+        return torch.cat([cheb_supports_apply(fwd, x),
+                          cheb_supports_apply(bwd, x)[:, 1:]], dim=1)
     G = torch.sparse_csr_tensor(
         csr.row_ptr.to(torch.int64), csr.col_idx.to(torch.int64),
         csr.vals.to(x.dtype), size=(csr.n_nodes, csr.n_nodes), device=x.device)
@@ -61,7 +66,8 @@ def cheb_supports_apply(csr, x: torch.Tensor) -> torch.Tensor:
 def gconv_mix_csr(csr, x: torch.Tensor, W: torch.Tensor,
                   b: Optional[torch.Tensor], activation: Optional[str]) -> torch.Tensor:
     """CSR path of gconv_mix: same math as gconv_mix_dense with the support
-    stack generated on the fly by the Chebyshev recurrence."""
+    stack generated on the fly by the Chebyshev recurrence (one generator,
+    or the two of a "dual" support)."""
     B, N, C = x.shape
     S = cheb_supports_apply(csr, x)                 # (B, K, N, C)
     feat = S.permute(0, 2, 1, 3).reshape(B, N, csr.K_supports * C)
