@@ -1,16 +1,11 @@
 // Python bindings + host-side sequencing for the stmgcn_amd HIP kernels.
 // Device code lives in the .hip translation units (pure HIP, no torch);
 // this file owns at::Tensor plumbing, stream lookup and launch ordering.
+// The entry points and their argument structs are declared once, in kernels.h.
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-extern "C" void stmgcn_spmm_step(
-    void* stream, int dtype, const int* rowptr, const int* colidx,
-    const float* vals, const void* xin, const void* p1, const void* p2,
-    void* out, int B, int N, int C,
-    long sx, long s1, long s2, long so,
-    long bx, long b1, long b2, long bo,
-    float alpha, float beta, float gamma);
+#include "kernels.h"
 
 namespace {
 
@@ -25,21 +20,54 @@ int dtype_code(const at::Tensor& t) {
 
 void* stream() { return (void*)at::cuda::getCurrentCUDAStream().stream(); }
 
+// The only way a binding obtains CSR pointers: the kernels index rowptr[0..N]
+// and colidx/vals unchecked, so a CSR for another N must not reach them.
+StmCsr csr_ptrs(const at::Tensor& rowptr, const at::Tensor& colidx,
+                const at::Tensor& vals, int N) {
+  TORCH_CHECK(rowptr.is_cuda() && colidx.is_cuda() && vals.is_cuda());
+  TORCH_CHECK(rowptr.scalar_type() == at::kInt && colidx.scalar_type() == at::kInt &&
+              vals.scalar_type() == at::kFloat);
+  TORCH_CHECK(rowptr.is_contiguous() && colidx.is_contiguous() && vals.is_contiguous());
+  TORCH_CHECK(rowptr.numel() == N + 1 && colidx.numel() == vals.numel());
+  return {rowptr.data_ptr<int>(), colidx.data_ptr<int>(), vals.data_ptr<float>()};
+}
+
+// bias pointer for a fused forward; `keep` owns the contiguous copy for the
+// duration of the binding (a temporary would be freed before the launches)
+const void* bias_ptr(const c10::optional<at::Tensor>& bias, const at::Tensor& x,
+                     int Cout, at::Tensor& keep) {
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->scalar_type() == x.scalar_type() && bias->numel() == Cout);
+  keep = bias->contiguous();
+  return keep.data_ptr();
+}
+
+// optional fp32 (N,) accumulator of the wgrad kernels
+float* db_ptr(const c10::optional<at::Tensor>& db, int N) {
+  if (!db.has_value()) return nullptr;
+  TORCH_CHECK(db->is_contiguous() && db->scalar_type() == at::kFloat && db->numel() == N);
+  return db->data_ptr<float>();
+}
+
 struct Slice {
   const void* ptr;
   long srow, sbatch;
 };
+const Slice kNone{nullptr, 0, 0};
 
 // one recurrence step: out_slice = alpha * G @ x_slice + beta*p1 + gamma*p2
-void step(int dt, const at::Tensor& rowptr, const at::Tensor& colidx,
-          const at::Tensor& vals, Slice xin, Slice p1, Slice p2,
-          void* out, long so, long bo, int B, int N, int C,
-          float alpha, float beta, float gamma) {
-  stmgcn_spmm_step(stream(), dt, rowptr.data_ptr<int>(), colidx.data_ptr<int>(),
-                   vals.data_ptr<float>(), xin.ptr, p1.ptr, p2.ptr, out,
-                   B, N, C, xin.srow, p1.srow, p2.srow, so,
-                   xin.sbatch, p1.sbatch, p2.sbatch, bo, alpha, beta, gamma);
-}
+struct SpmmStep {
+  int dt;
+  StmCsr g;
+  int B, N, C;
+  void operator()(Slice xin, Slice p1, Slice p2, Slice out, float alpha,
+                  float beta, float gamma) const {
+    stmgcn_spmm_step(stream(), dt, g.rowptr, g.colidx, g.vals, xin.ptr, p1.ptr,
+                     p2.ptr, const_cast<void*>(out.ptr), B, N, C, xin.srow,
+                     p1.srow, p2.srow, out.srow, xin.sbatch, p1.sbatch,
+                     p2.sbatch, out.sbatch, alpha, beta, gamma);
+  }
+};
 
 }  // namespace
 
@@ -48,33 +76,24 @@ void step(int dt, const at::Tensor& rowptr, const at::Tensor& colidx,
 at::Tensor cheb_apply(at::Tensor x, at::Tensor rowptr, at::Tensor colidx,
                       at::Tensor vals, int64_t K_s, bool single) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous());
-  TORCH_CHECK(rowptr.scalar_type() == at::kInt && colidx.scalar_type() == at::kInt);
-  TORCH_CHECK(vals.scalar_type() == at::kFloat);
   const int B = x.size(0), N = x.size(1), C = x.size(2);
-  const int dt = dtype_code(x);
+  const SpmmStep step{dtype_code(x), csr_ptrs(rowptr, colidx, vals, N), B, N, C};
   auto S = at::empty({B, N, K_s, C}, x.options());
   const long es = x.element_size();
-  const char* xp = (const char*)x.data_ptr();
   char* Sp = (char*)S.data_ptr();
-  const long sx = C, bx = (long)N * C;              // x row/batch strides (elems)
   const long so = K_s * (long)C, bo = (long)N * K_s * C;  // S row/batch strides
   auto sl = [&](int k) -> Slice { return {Sp + (long)k * C * es, so, bo}; };
-  const Slice none{nullptr, 0, 0};
-  const Slice xs{xp, sx, bx};
+  const Slice xs{x.data_ptr(), C, (long)N * C};
 
   if (single) {
     TORCH_CHECK(K_s == 1);
-    step(dt, rowptr, colidx, vals, xs, none, none, Sp, so, bo, B, N, C, 1.f, 0.f, 0.f);
+    step(xs, kNone, kNone, sl(0), 1.f, 0.f, 0.f);
     return S;
   }
-  // T_0 x = x (copy into slice 0)
-  step(dt, rowptr, colidx, vals, none, none, xs, Sp, so, bo, B, N, C, 0.f, 0.f, 1.f);
-  if (K_s > 1)  // T_1 x = G x
-    step(dt, rowptr, colidx, vals, xs, none, none, (char*)sl(1).ptr, so, bo,
-         B, N, C, 1.f, 0.f, 0.f);
+  step(kNone, kNone, xs, sl(0), 0.f, 0.f, 1.f);   // T_0 x = x (copy into slice 0)
+  if (K_s > 1) step(xs, kNone, kNone, sl(1), 1.f, 0.f, 0.f);   // T_1 x = G x
   for (int k = 2; k < K_s; ++k)  // T_k x = 2 G (T_{k-1} x) - T_{k-2} x
-    step(dt, rowptr, colidx, vals, sl(k - 1), sl(k - 2), none,
-         (char*)sl(k).ptr, so, bo, B, N, C, 2.f, -1.f, 0.f);
+    step(sl(k - 1), sl(k - 2), kNone, sl(k), 2.f, -1.f, 0.f);
   return S;
 }
 
@@ -85,168 +104,126 @@ at::Tensor cheb_combine(at::Tensor U, at::Tensor rowptr, at::Tensor colidx,
                         at::Tensor vals, bool single) {
   TORCH_CHECK(U.is_cuda() && U.dim() == 4 && U.is_contiguous());
   const int B = U.size(0), N = U.size(1), K_s = U.size(2), C = U.size(3);
-  const int dt = dtype_code(U);
+  const SpmmStep step{dtype_code(U), csr_ptrs(rowptr, colidx, vals, N), B, N, C};
   auto Z = at::empty({B, N, C}, U.options());
   const long es = U.element_size();
   const char* Up = (const char*)U.data_ptr();
   const long su = (long)K_s * C, bu = (long)N * K_s * C;
   const long sz = C, bz = (long)N * C;
   auto ul = [&](int k) -> Slice { return {Up + (long)k * C * es, su, bu}; };
-  const Slice none{nullptr, 0, 0};
+  const Slice Zs{Z.data_ptr(), sz, bz};
 
-  if (single || K_s == 1) {
-    // Z = G^T U_0 (single) or T_0-only cheby (Z = U_0 — alpha 0 copy)
-    if (single)
-      step(dt, rowptr, colidx, vals, ul(0), none, none, Z.data_ptr(), sz, bz,
-           B, N, C, 1.f, 0.f, 0.f);
-    else
-      step(dt, rowptr, colidx, vals, none, none, ul(0), Z.data_ptr(), sz, bz,
-           B, N, C, 0.f, 0.f, 1.f);
+  if (single) {  // Z = G^T U_0
+    step(ul(0), kNone, kNone, Zs, 1.f, 0.f, 0.f);
     return Z;
   }
-
   const int K = K_s - 1;
+  if (K == 0) {  // T_0-only cheby: Z = U_0 (alpha 0 copy)
+    step(kNone, kNone, ul(0), Zs, 0.f, 0.f, 1.f);
+    return Z;
+  }
   if (K == 1) {  // Z = U_0 + G U_1
-    step(dt, rowptr, colidx, vals, ul(1), none, ul(0), Z.data_ptr(), sz, bz,
-         B, N, C, 1.f, 0.f, 1.f);
+    step(ul(1), kNone, ul(0), Zs, 1.f, 0.f, 1.f);
     return Z;
   }
   auto bk1 = at::empty({B, N, C}, U.options());   // b_{j+1}
   at::Tensor bk2;                                  // b_{j+2}; empty = virtual 0
-  // b_K = U_K  (copy)
-  step(dt, rowptr, colidx, vals, none, none, ul(K), bk1.data_ptr(), sz, bz,
-       B, N, C, 0.f, 0.f, 1.f);
-  Slice sb1{bk1.data_ptr(), sz, bz}, sb2 = none;
+  Slice sb1{bk1.data_ptr(), sz, bz}, sb2 = kNone;
+  step(kNone, kNone, ul(K), sb1, 0.f, 0.f, 1.f);   // b_K = U_K  (copy)
   for (int j = K - 1; j >= 1; --j) {
     auto bnew = at::empty({B, N, C}, U.options());
     // b_j = 2 G b_{j+1} - b_{j+2} + U_j   (p1 = b_{j+2}, p2 = U_j);
     // b_{K+1} == 0 -> p1 skipped (beta 0) on the first iteration
-    step(dt, rowptr, colidx, vals, sb1, sb2, ul(j), bnew.data_ptr(), sz, bz,
-         B, N, C, 2.f, sb2.ptr ? -1.f : 0.f, 1.f);
+    step(sb1, sb2, ul(j), {bnew.data_ptr(), sz, bz}, 2.f, sb2.ptr ? -1.f : 0.f, 1.f);
     bk2 = bk1; bk1 = bnew;
     sb1 = {bk1.data_ptr(), sz, bz}; sb2 = {bk2.data_ptr(), sz, bz};
   }
-  // Z = G b_1 - b_2 + U_0
-  step(dt, rowptr, colidx, vals, sb1, sb2, ul(0), Z.data_ptr(), sz, bz,
-       B, N, C, 1.f, -1.f, 1.f);
+  step(sb1, sb2, ul(0), Zs, 1.f, -1.f, 1.f);   // Z = G b_1 - b_2 + U_0
   return Z;
 }
 
 // ---------------------------------------------------------------------------
 // Fully fused ChebConv (SURVEY K1+K2): recurrence + MFMA mix + bias + act in
 // one kernel chain; no support stack, no library GEMMs.
-
-extern "C" void stmgcn_cheb_fused_fwd_step(
-    void* stream, int dtype, const int* rowptr, const int* colidx,
-    const float* vals, const void* xin, const void* p1, const void* x0,
-    const void* W, const void* bias, void* pout, float* yacc, void* yout,
-    int B, int N, int C, int Cout, int kofs, float alpha, float beta,
-    int first, int act);
-extern "C" void stmgcn_cheb_fused_bwd_step(
-    void* stream, int dtype, const int* rowptr, const int* colidx,
-    const float* vals, const void* xin, const void* p1, const void* dz,
-    const void* W, void* out, int B, int N, int C, int Cout, int kofs,
-    float alpha, float beta);
+// A binding fills one argument struct (kernels.h) per call chain and changes
+// only the per-step fields between launches.
 
 // y = act(sum_k (T_k(G) x) @ W_k + b), fused: the K_s recurrence steps each
 // fold their mix into an fp32 accumulator; the last adds bias + activation.
 // Serves C <= 64, Cout <= 64 (every BASELINE config; the stack path in
-// cheb_apply remains for parity tests / larger widths).
-//
-// training=true additionally returns the recurrence states p_1..p_{K_s-1}
-// (p_0 == x) for the backward wgrad: the ping/pong state writes are
-// mandatory anyway (cross-workgroup recurrence dependency), so keeping them
-// costs ZERO extra HBM traffic — unlike the reference-style (B,N,K_s,C)
-// concat stack, which existed only to feed a library GEMM and is gone.
+// cheb_apply remains for parity tests / larger widths). training=true also
+// returns the recurrence states p_1..p_{K_s-1} (p_0 == x) for the wgrad: their
+// writes are mandatory anyway (cross-workgroup recurrence dependency), so
+// keeping them costs no extra HBM traffic, unlike a (B,N,K_s,C) concat stack.
 std::vector<at::Tensor> cheb_gconv_fused_fwd(
     at::Tensor x, at::Tensor rowptr, at::Tensor colidx, at::Tensor vals,
     at::Tensor W, c10::optional<at::Tensor> bias, int64_t K_s, bool single,
     int64_t act, bool training) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous());
   TORCH_CHECK(W.is_contiguous() && W.scalar_type() == x.scalar_type());
-  const int B = x.size(0), N = x.size(1), C = x.size(2);
-  const int Cout = W.size(1);
+  const int B = x.size(0), N = x.size(1), C = x.size(2), Cout = W.size(1);
   TORCH_CHECK(C <= 64 && Cout <= 64, "fused ChebConv serves C/Cout <= 64");
   TORCH_CHECK(W.size(0) == K_s * C);
   const int dt = dtype_code(x);
   void* st = stream();
-  const int* rp = rowptr.data_ptr<int>();
-  const int* ci = colidx.data_ptr<int>();
-  const float* v = vals.data_ptr<float>();
   auto y = at::empty({B, N, Cout}, x.options());
-  const void* bp = bias.has_value() ? bias->contiguous().data_ptr() : nullptr;
-  const int actc = (int)act;
+  at::Tensor bc;
+  ChebFwdArgs a;   // the fields every step of the chain shares
+  a.g = csr_ptrs(rowptr, colidx, vals, N);
+  a.W = W.data_ptr();
+  a.bias = bias_ptr(bias, x, Cout, bc);
+  a.B = B; a.N = N; a.C = C; a.Cout = Cout; a.act = (int)act;
 
   if (single) {  // localpool: y = act((G @ x) @ W + b); p = G x kept if training
     TORCH_CHECK(K_s == 1);
     at::Tensor p;
-    void* pp = nullptr;
-    if (training) {
-      p = at::empty({B, N, C}, x.options());
-      pp = p.data_ptr();
-    }
-    stmgcn_cheb_fused_fwd_step(st, dt, rp, ci, v, x.data_ptr(), nullptr,
-                               nullptr, W.data_ptr(), bp, pp, nullptr,
-                               y.data_ptr(), B, N, C, Cout, 0, 1.f, 0.f, 1,
-                               actc);
-    return training ? std::vector<at::Tensor>{y, p}
-                    : std::vector<at::Tensor>{y};
+    if (training) a.pout = (p = at::empty({B, N, C}, x.options())).data_ptr();
+    a.xin = x.data_ptr(); a.yout = y.data_ptr();
+    stmgcn_cheb_fused_fwd_step(st, dt, a);
+    return training ? std::vector<at::Tensor>{y, p} : std::vector<at::Tensor>{y};
   }
   if (K_s == 1) {  // T_0 only: y = act(x @ W + b)
-    stmgcn_cheb_fused_fwd_step(st, dt, rp, ci, v, nullptr, x.data_ptr(),
-                               nullptr, W.data_ptr(), bp, nullptr, nullptr,
-                               y.data_ptr(), B, N, C, Cout, 0, 0.f, 1.f, 1,
-                               actc);
+    a.p1 = x.data_ptr(); a.yout = y.data_ptr();
+    a.alpha = 0.f; a.beta = 1.f;
+    stmgcn_cheb_fused_fwd_step(st, dt, a);
     return {y};
   }
   // K_s - 1 launches: the T_0 mix (x @ W_0) rides the T_1 launch as its
   // x0 operand, so K_s == 2 needs no fp32 accumulator at all.
   at::Tensor yacc;
-  float* ya = nullptr;
   if (K_s > 2) {
     yacc = at::empty({B, N, Cout}, x.options().dtype(at::kFloat));
-    ya = yacc.data_ptr<float>();
+    a.yacc = yacc.data_ptr<float>();
   }
-  // recurrence states; training keeps every p_k (zero extra traffic — the
-  // writes are mandatory), eval ping/pongs two buffers.
+  // training keeps every p_k, eval ping/pongs two buffers
   std::vector<at::Tensor> ps;
   const int nbuf = training ? (int)K_s - 1 : std::min<int>(2, (int)K_s - 1);
   for (int i = 0; i < nbuf; ++i)
     ps.push_back(at::empty({B, N, C}, x.options()));
   // k = 1: p_1 = G x; y (+)= x @ W_0 + p_1 @ W_1
-  bool last = (K_s == 2);
-  stmgcn_cheb_fused_fwd_step(st, dt, rp, ci, v, x.data_ptr(), nullptr,
-                             x.data_ptr(), W.data_ptr(), bp,
-                             ps[0].data_ptr(), ya,
-                             last ? y.data_ptr() : nullptr, B, N, C, Cout,
-                             C, 1.f, 0.f, 1, actc);
-  // k >= 2: p_k = 2 G p_{k-1} - p_{k-2}; p1 == pout aliasing is element-safe
-  const void* pm2 = x.data_ptr();
-  void* pm1 = ps[0].data_ptr();
-  for (int k = 2; k < K_s; ++k) {
-    void* dst = training ? ps[k - 1].data_ptr()
-                         : (k == 2 ? ps[1].data_ptr()
-                                   : const_cast<void*>(pm2));
-    last = (k == K_s - 1);
-    stmgcn_cheb_fused_fwd_step(st, dt, rp, ci, v, pm1, pm2, nullptr,
-                               W.data_ptr(), bp, dst, ya,
-                               last ? y.data_ptr() : nullptr, B, N,
-                               C, Cout, k * C, 2.f, -1.f, 0, actc);
-    pm2 = pm1;
-    pm1 = dst;
+  // k >= 2: p_k = 2 G p_{k-1} - p_{k-2}, y += p_k @ W_k; eval writes p_k over
+  // p_{k-2} from k = 3 on (never over x): p1 == pout aliasing is element-safe
+  const void* pm2 = nullptr;          // p_{k-2}
+  a.xin = a.x0 = x.data_ptr();        // p_{k-1}
+  for (int k = 1; k < K_s; ++k) {
+    a.p1 = pm2;
+    a.pout = (training || k <= 2) ? ps[k - 1].data_ptr() : const_cast<void*>(pm2);
+    a.kofs = k * C;
+    a.yout = k == K_s - 1 ? y.data_ptr() : nullptr;
+    stmgcn_cheb_fused_fwd_step(st, dt, a);
+    pm2 = a.xin; a.xin = a.pout; a.x0 = nullptr;
+    a.alpha = 2.f; a.beta = -1.f; a.first = 0;
   }
-  if (!training) return {y};
   std::vector<at::Tensor> out{y};
-  for (auto& p : ps) out.push_back(p);
+  if (training) out.insert(out.end(), ps.begin(), ps.end());
   return out;
 }
 
 // dX = sum_k T_k(G)^T (dz W_k^T) via Clenshaw over the G^T CSR with the
 // U_j = dz W_j^T term fused into every step (never materialized).
-at::Tensor cheb_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W,
-                                   at::Tensor rowptr_t, at::Tensor colidx_t,
-                                   at::Tensor vals_t, int64_t K_s,
-                                   bool single) {
+at::Tensor cheb_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W, at::Tensor rowptr_t,
+                                   at::Tensor colidx_t, at::Tensor vals_t,
+                                   int64_t K_s, bool single) {
   TORCH_CHECK(dz.is_cuda() && dz.dim() == 3 && dz.is_contiguous());
   TORCH_CHECK(W.is_contiguous() && W.scalar_type() == dz.scalar_type());
   const int B = dz.size(0), N = dz.size(1), Cout = dz.size(2);
@@ -254,24 +231,27 @@ at::Tensor cheb_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W,
   TORCH_CHECK(C <= 64 && Cout <= 64 && (int)(K_s * C) == W.size(0));
   const int dt = dtype_code(dz);
   void* st = stream();
-  const int* rp = rowptr_t.data_ptr<int>();
-  const int* ci = colidx_t.data_ptr<int>();
-  const float* v = vals_t.data_ptr<float>();
   auto dX = at::empty({B, N, C}, dz.options());
+  ChebBwdArgs a;
+  a.g = csr_ptrs(rowptr_t, colidx_t, vals_t, N);
+  a.dz = dz.data_ptr(); a.W = W.data_ptr();
+  a.B = B; a.N = N; a.C = C; a.Cout = Cout;
 
   auto bwd = [&](const void* xin, const void* p1, void* out, int kofs,
                  float alpha, float beta) {
-    stmgcn_cheb_fused_bwd_step(st, dt, rp, ci, v, xin, p1, dz.data_ptr(),
-                               W.data_ptr(), out, B, N, C, Cout, kofs, alpha,
-                               beta);
+    a.xin = xin; a.p1 = p1; a.out = out;
+    a.kofs = kofs; a.alpha = alpha; a.beta = beta;
+    stmgcn_cheb_fused_bwd_step(st, dt, a);
   };
   if (single) {  // dX = G^T U_0: materialize U_0, then one plain SpMM
     auto U0 = at::empty({B, N, C}, dz.options());
     bwd(nullptr, nullptr, U0.data_ptr(), 0, 0.f, 0.f);
-    stmgcn_cheb_fused_fwd_step(st, dt, rp, ci, v, U0.data_ptr(), nullptr,
-                               nullptr, nullptr, nullptr, dX.data_ptr(),
-                               nullptr, nullptr, B, N, C, C, 0, 1.f, 0.f, 1,
-                               0);
+    ChebFwdArgs s;   // W == null: no mix
+    s.g = a.g;
+    s.xin = U0.data_ptr();
+    s.pout = dX.data_ptr();
+    s.B = B; s.N = N; s.C = s.Cout = C;
+    stmgcn_cheb_fused_fwd_step(st, dt, s);
     return dX;
   }
   const int K = (int)K_s - 1;
@@ -279,66 +259,28 @@ at::Tensor cheb_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W,
     bwd(nullptr, nullptr, dX.data_ptr(), 0, 0.f, 0.f);
     return dX;
   }
-  if (K == 1) {  // dX = U_0 + G^T U_1
-    auto b1 = at::empty({B, N, C}, dz.options());
-    bwd(nullptr, nullptr, b1.data_ptr(), C, 0.f, 0.f);
-    bwd(b1.data_ptr(), nullptr, dX.data_ptr(), 0, 1.f, 0.f);
-    return dX;
-  }
-  // general Clenshaw: b_K = U_K; b_j = U_j + 2 G^T b_{j+1} - b_{j+2};
-  // dX = U_0 + G^T b_1 - b_2. Two ping/pong buffers; p1 aliasing is safe.
+  // Clenshaw: b_K = U_K; b_j = U_j + 2 G^T b_{j+1} - b_{j+2};
+  // dX = U_0 + G^T b_1 - b_2 (K == 1: dX = U_0 + G^T U_1, b_2 absent). Two
+  // ping/pong buffers (one for K == 1); p1 aliasing is safe.
   auto bufA = at::empty({B, N, C}, dz.options());
-  auto bufB = at::empty({B, N, C}, dz.options());
+  auto bufB = K > 1 ? at::empty({B, N, C}, dz.options()) : at::Tensor();
   void* bj1 = bufA.data_ptr();  // b_{j+1}
   void* bj2 = nullptr;          // b_{j+2}
   bwd(nullptr, nullptr, bj1, K * C, 0.f, 0.f);  // b_K
-  void* other = bufB.data_ptr();
+  void* other = K > 1 ? bufB.data_ptr() : nullptr;
   for (int j = K - 1; j >= 1; --j) {
     bwd(bj1, bj2, other, j * C, 2.f, bj2 ? -1.f : 0.f);
     bj2 = bj1;
     bj1 = other;
     other = bj2;  // overwritten next iteration (element-wise p1 read is safe)
   }
-  bwd(bj1, bj2, dX.data_ptr(), 0, 1.f, -1.f);
+  bwd(bj1, bj2, dX.data_ptr(), 0, 1.f, bj2 ? -1.f : 0.f);
   return dX;
 }
 
 // ---------------------------------------------------------------------------
 // Dual random-walk diffusion gconv (dual_gconv.hip): 2K+1 supports
 // [I, T_1..T_K(G_f), T_1..T_K(G_b)], both generators advanced per launch.
-
-extern "C" void stmgcn_dual_fused_fwd_step(
-    void* stream, int dtype, const int* rpf, const int* cif, const float* vf,
-    const int* rpb, const int* cib, const float* vb, const void* xf,
-    const void* pf1, const void* xb, const void* pb1, const void* x0,
-    const void* W, const void* bias, void* pfout, void* pbout, float* yacc,
-    void* yout, int B, int N, int C, int Cout, int kofs_f, int kofs_b,
-    float alpha, float beta, int first, int act);
-extern "C" void stmgcn_dual_fused_bwd_step(
-    void* stream, int dtype, const int* rpf, const int* cif, const float* vf,
-    const int* rpb, const int* cib, const float* vb, const void* xf,
-    const void* pf1, const void* xb, const void* pb1, const void* dz,
-    const void* W, void* outf, void* outb, int B, int N, int C, int Cout,
-    int kofs_f, int kofs_b, float alpha, float beta, int final_step);
-
-namespace {
-
-struct CsrPtrs {
-  const int *rp, *ci;
-  const float* v;
-};
-
-CsrPtrs csr_ptrs(const at::Tensor& rowptr, const at::Tensor& colidx,
-                 const at::Tensor& vals, int N) {
-  TORCH_CHECK(rowptr.is_cuda() && colidx.is_cuda() && vals.is_cuda());
-  TORCH_CHECK(rowptr.scalar_type() == at::kInt && colidx.scalar_type() == at::kInt &&
-              vals.scalar_type() == at::kFloat);
-  TORCH_CHECK(rowptr.is_contiguous() && colidx.is_contiguous() && vals.is_contiguous());
-  TORCH_CHECK(rowptr.numel() == N + 1 && colidx.numel() == vals.numel());
-  return {rowptr.data_ptr<int>(), colidx.data_ptr<int>(), vals.data_ptr<float>()};
-}
-
-}  // namespace
 
 // y = act(x W_0 + sum_k (T_k(G_f) x) W_k + (T_k(G_b) x) W_{K+k} + b) in K
 // launches. training=true additionally returns pf_1..pf_K, pb_1..pb_K for the
@@ -351,27 +293,24 @@ std::vector<at::Tensor> dual_gconv_fused_fwd(
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf,
               "fused dual gconv serves bf16/f16");
   TORCH_CHECK(W.is_contiguous() && W.scalar_type() == x.scalar_type());
-  const int B = x.size(0), N = x.size(1), C = x.size(2);
-  const int Cout = W.size(1);
+  const int B = x.size(0), N = x.size(1), C = x.size(2), Cout = W.size(1);
   TORCH_CHECK(K >= 1 && C <= 64 && Cout <= 64,
               "fused dual gconv serves K >= 1, C/Cout <= 64");
   TORCH_CHECK(W.size(0) == (2 * K + 1) * C);
   const int dt = dtype_code(x);
   void* st = stream();
-  const CsrPtrs gf = csr_ptrs(rpf, cif, vf, N), gb = csr_ptrs(rpb, cib, vb, N);
+  DualFwdArgs a;
+  a.gf = csr_ptrs(rpf, cif, vf, N);
+  a.gb = csr_ptrs(rpb, cib, vb, N);
   auto y = at::empty({B, N, Cout}, x.options());
   at::Tensor bc;
-  const void* bp = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->scalar_type() == x.scalar_type() && bias->numel() == Cout);
-    bc = bias->contiguous();
-    bp = bc.data_ptr();
-  }
+  a.W = W.data_ptr();
+  a.bias = bias_ptr(bias, x, Cout, bc);
+  a.B = B; a.N = N; a.C = C; a.Cout = Cout; a.act = (int)act;
   at::Tensor yacc;
-  float* ya = nullptr;
   if (K > 1) {
     yacc = at::empty({B, N, Cout}, x.options().dtype(at::kFloat));
-    ya = yacc.data_ptr<float>();
+    a.yacc = yacc.data_ptr<float>();
   }
   const int nbuf = training ? (int)K : std::min<int>(2, (int)K);
   std::vector<at::Tensor> pf, pb;
@@ -380,26 +319,20 @@ std::vector<at::Tensor> dual_gconv_fused_fwd(
     pb.push_back(at::empty({B, N, C}, x.options()));
   }
   // k = 1: p_1 = G x (both directions); acc = x W_0 + pf_1 W_1 + pb_1 W_{K+1}
-  stmgcn_dual_fused_fwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
-                             x.data_ptr(), nullptr, x.data_ptr(), nullptr,
-                             x.data_ptr(), W.data_ptr(), bp, pf[0].data_ptr(),
-                             pb[0].data_ptr(), ya,
-                             K == 1 ? y.data_ptr() : nullptr, B, N, C, Cout,
-                             C, (int)(K + 1) * C, 1.f, 0.f, 1, (int)act);
   // k >= 2: p_k = 2 G p_{k-1} - p_{k-2}; eval writes p_k over p_{k-2} from
   // k = 3 on (never over x) — the p1 == pout aliasing the kernel allows
-  const void *f2 = x.data_ptr(), *b2 = x.data_ptr();
-  void *f1 = pf[0].data_ptr(), *b1 = pb[0].data_ptr();
-  for (int k = 2; k <= K; ++k) {
-    void* df = (training || k == 2) ? pf[k - 1].data_ptr() : const_cast<void*>(f2);
-    void* db = (training || k == 2) ? pb[k - 1].data_ptr() : const_cast<void*>(b2);
-    stmgcn_dual_fused_fwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
-                               f1, f2, b1, b2, nullptr, W.data_ptr(), bp, df,
-                               db, ya, k == K ? y.data_ptr() : nullptr, B, N,
-                               C, Cout, k * C, (int)(K + k) * C, 2.f, -1.f, 0,
-                               (int)act);
-    f2 = f1; f1 = df;
-    b2 = b1; b1 = db;
+  const void *f2 = nullptr, *b2 = nullptr;   // p_{k-2}
+  a.xf = a.xb = a.x0 = x.data_ptr();         // p_{k-1}
+  for (int k = 1; k <= K; ++k) {
+    a.pf1 = f2; a.pb1 = b2;
+    const bool fresh = training || k <= 2;
+    a.pfout = fresh ? pf[k - 1].data_ptr() : const_cast<void*>(f2);
+    a.pbout = fresh ? pb[k - 1].data_ptr() : const_cast<void*>(b2);
+    a.kofs_f = k * C; a.kofs_b = (int)(K + k) * C;
+    a.yout = k == K ? y.data_ptr() : nullptr;
+    stmgcn_dual_fused_fwd_step(st, dt, a);
+    f2 = a.xf; b2 = a.xb; a.xf = a.pfout; a.xb = a.pbout; a.x0 = nullptr;
+    a.alpha = 2.f; a.beta = -1.f; a.first = 0;
   }
   std::vector<at::Tensor> out{y};
   if (training) {
@@ -412,9 +345,8 @@ std::vector<at::Tensor> dual_gconv_fused_fwd(
 // dX = U_0 + sum_k T_k(G_f)^T U_k + T_k(G_b)^T U_{K+k}, U_j = dz W_j^T, via
 // two Clenshaw chains over the transposed CSRs advanced together: K+1 launches.
 at::Tensor dual_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W, at::Tensor rpf_t,
-                                   at::Tensor cif_t, at::Tensor vf_t,
-                                   at::Tensor rpb_t, at::Tensor cib_t,
-                                   at::Tensor vb_t, int64_t K) {
+                                   at::Tensor cif_t, at::Tensor vf_t, at::Tensor rpb_t,
+                                   at::Tensor cib_t, at::Tensor vb_t, int64_t K) {
   TORCH_CHECK(dz.is_cuda() && dz.dim() == 3 && dz.is_contiguous());
   TORCH_CHECK(dz.scalar_type() == at::kBFloat16 || dz.scalar_type() == at::kHalf,
               "fused dual gconv serves bf16/f16");
@@ -425,17 +357,21 @@ at::Tensor dual_gconv_fused_bwd_dx(at::Tensor dz, at::Tensor W, at::Tensor rpf_t
   TORCH_CHECK(C <= 64 && Cout <= 64);
   const int dt = dtype_code(dz);
   void* st = stream();
-  const CsrPtrs gf = csr_ptrs(rpf_t, cif_t, vf_t, N),
-                gb = csr_ptrs(rpb_t, cib_t, vb_t, N);
+  DualBwdArgs a;
+  a.gft = csr_ptrs(rpf_t, cif_t, vf_t, N);
+  a.gbt = csr_ptrs(rpb_t, cib_t, vb_t, N);
+  a.dz = dz.data_ptr(); a.W = W.data_ptr();
+  a.B = B; a.N = N; a.C = C; a.Cout = Cout;
   auto dX = at::empty({B, N, C}, dz.options());
 
   auto bwd = [&](const void* xf, const void* pf1, const void* xb,
                  const void* pb1, void* outf, void* outb, int j, float alpha,
                  float beta) {
-    stmgcn_dual_fused_bwd_step(st, dt, gf.rp, gf.ci, gf.v, gb.rp, gb.ci, gb.v,
-                               xf, pf1, xb, pb1, dz.data_ptr(), W.data_ptr(),
-                               outf, outb, B, N, C, Cout, j * C,
-                               (int)(K + j) * C, alpha, beta, j == 0);
+    a.xf = xf; a.pf1 = pf1; a.xb = xb; a.pb1 = pb1;
+    a.outf = outf; a.outb = outb; a.final_step = j == 0;
+    a.kofs_f = j * C; a.kofs_b = (int)(K + j) * C;
+    a.alpha = alpha; a.beta = beta;
+    stmgcn_dual_fused_bwd_step(st, dt, a);
   };
   // b_K = U_K; b_j = U_j + 2 G^T b_{j+1} - b_{j+2}; dX = U_0 + sum over both
   // chains of (G^T b_1 - b_2). Two ping/pong buffers per direction.
@@ -465,13 +401,14 @@ at::Tensor spmm_axpby(at::Tensor xin, c10::optional<at::Tensor> p1,
   TORCH_CHECK(xin.is_cuda() && xin.dim() == 3 && xin.is_contiguous());
   const int B = xin.size(0), N = xin.size(1), C = xin.size(2);
   auto out = at::empty_like(xin);
-  stmgcn_cheb_fused_fwd_step(stream(), dtype_code(xin),
-                             rowptr.data_ptr<int>(), colidx.data_ptr<int>(),
-                             vals.data_ptr<float>(), xin.data_ptr(),
-                             p1.has_value() ? p1->data_ptr() : nullptr,
-                             nullptr, nullptr, nullptr, out.data_ptr(),
-                             nullptr, nullptr, B, N, C, C, 0, (float)alpha,
-                             (float)beta, 1, 0);
+  ChebFwdArgs a;   // W == null: no mix
+  a.g = csr_ptrs(rowptr, colidx, vals, N);
+  a.xin = xin.data_ptr();
+  a.p1 = p1.has_value() ? p1->data_ptr() : nullptr;
+  a.pout = out.data_ptr();
+  a.B = B; a.N = N; a.C = a.Cout = C;
+  a.alpha = (float)alpha; a.beta = (float)beta;
+  stmgcn_cheb_fused_fwd_step(stream(), dtype_code(xin), a);
   return out;
 }
 
@@ -481,33 +418,6 @@ at::Tensor spmm_axpby(at::Tensor xin, c10::optional<at::Tensor> p1,
 // (L, Tst, S_pad, 4H) but each 32-row sequence tile stored in the wgrad MFMA
 // fragment order documented in csrc/common.h; lstm_wgrad expects that order.
 
-extern "C" void stmgcn_lstm_fwd(void* stream, int dtype, const void* x,
-                                void* out, void* hseq_g, void* cseq_g,
-                                void* gates_g, const void** w_ih,
-                                const void** w_hh, const void** b_ih,
-                                const void** b_hh, int S, int Tst, int L,
-                                int cin, int ret_seq, int gru);
-extern "C" void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout,
-                                const void* x, const void* cseq_g,
-                                const void* gates_g, const void** w_ihT,
-                                const void** w_hhT, void* dx, void* dA_g,
-                                void* dh_g, int S, int Tst, int L, int cin,
-                                int ret_seq, int gru);
-extern "C" void stmgcn_mfma_probe(void* stream, const void* A, const void* B,
-                                  void* D);
-extern "C" void stmgcn_lstm_wgrad(void* stream, int dtype, const void* dA,
-                                  const void* hseq, const void* x, float* dwih,
-                                  float* dwhh, float* db, long R, long S_pad,
-                                  int S, int Tst, int L, int cin);
-extern "C" void stmgcn_atb_wgrad(void* stream, int dtype, const void* A,
-                                 const void* B, float* C, float* db, long rows,
-                                 int M, int N);
-extern "C" void stmgcn_atb_wgrad_multi(void* stream, int dtype,
-                                       const void** As, int nsrc, int CA,
-                                       const void* B, float* C, float* db,
-                                       long rows, int N);
-
-static constexpr int kSeqTile = 32;  // MUST match SEQ_TILE in common.h
 static constexpr int kH = 64;
 
 std::vector<at::Tensor> lstm_fwd(at::Tensor x, std::vector<at::Tensor> w_ih,
@@ -529,8 +439,8 @@ std::vector<at::Tensor> lstm_fwd(at::Tensor x, std::vector<at::Tensor> w_ih,
     TORCH_CHECK(b_ih[l].scalar_type() == x.scalar_type() &&
                 b_hh[l].scalar_type() == x.scalar_type());
   }
-  const long nblk = (S + kSeqTile - 1) / kSeqTile;
-  const long S_pad = nblk * kSeqTile;
+  const long nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
+  const long S_pad = nblk * SEQ_TILE;
   auto out = ret_seq ? at::empty({S, Tst, kH}, x.options())
                      : at::empty({S, kH}, x.options());
   at::Tensor hseq, cseq, gates;
@@ -565,8 +475,8 @@ std::vector<at::Tensor> lstm_bwd(at::Tensor dout, at::Tensor x,
   dout = dout.contiguous();
   const int S = x.size(0), Tst = x.size(1), cin = x.size(2);
   const int L = (int)w_ihT.size();
-  const long nblk = (S + kSeqTile - 1) / kSeqTile;
-  const long S_pad = nblk * kSeqTile;
+  const long nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
+  const long S_pad = nblk * SEQ_TILE;
   auto dx = at::empty_like(x);
   auto dA = at::empty({L, Tst, S_pad, 4 * kH}, x.options());
   // cross-layer dh hand-off scratch (global; LDS only holds dA tiles)
@@ -599,7 +509,7 @@ std::vector<at::Tensor> lstm_wgrad(at::Tensor dA, at::Tensor hseq, at::Tensor x)
   const long R = (long)Tst * S_pad;
   const int S = x.size(0), cin = x.size(2);
   TORCH_CHECK(cin == 1 || cin == kH);
-  TORCH_CHECK(dA.size(3) == 4 * kH && S_pad % kSeqTile == 0 && S <= S_pad,
+  TORCH_CHECK(dA.size(3) == 4 * kH && S_pad % SEQ_TILE == 0 && S <= S_pad,
               "dA must be (L, Tst, S_pad, 4H) with S_pad a multiple of 32");
   TORCH_CHECK(hseq.dim() == 4 && hseq.size(0) == L && hseq.size(1) == Tst &&
               hseq.size(2) == S_pad && hseq.size(3) == kH && x.size(1) == Tst);
@@ -646,12 +556,7 @@ void atb_wgrad_into(at::Tensor A, at::Tensor B, at::Tensor C,
   const int M = A.size(1), N = B.size(1);
   TORCH_CHECK(B.size(0) == rows && M <= 256 && N <= 64 && M % 8 == 0 && N % 8 == 0);
   TORCH_CHECK(C.size(0) == M && C.size(1) == N);
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    TORCH_CHECK(db->is_contiguous() && db->scalar_type() == at::kFloat &&
-                db->numel() == N);
-    dbp = db->data_ptr<float>();
-  }
+  float* dbp = db_ptr(db, N);
   stmgcn_atb_wgrad(stream(), dtype_code(A), A.data_ptr(), B.data_ptr(),
                    C.data_ptr<float>(), dbp, rows, M, N);
 }
@@ -676,12 +581,7 @@ void atb_wgrad_multi(std::vector<at::Tensor> As, at::Tensor B, at::Tensor C,
                 As[i].scalar_type() == B.scalar_type());
     srcs[i] = As[i].data_ptr();
   }
-  float* dbp = nullptr;
-  if (db.has_value()) {
-    TORCH_CHECK(db->is_contiguous() && db->scalar_type() == at::kFloat &&
-                db->numel() == N);
-    dbp = db->data_ptr<float>();
-  }
+  float* dbp = db_ptr(db, N);
   stmgcn_atb_wgrad_multi(stream(), dtype_code(B), srcs, (int)As.size(), CA,
                          B.data_ptr(), C.data_ptr<float>(), dbp, rows, N);
 }
@@ -696,28 +596,6 @@ at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
 
 // ---------------------------------------------------------------------------
 // pointwise.hip ops: K3 seqsum/permute, K4 gate, K7 head, K8 loss, K9 Adam
-
-extern "C" {
-void stmgcn_seqsum_permute(void*, int, const void*, void*, int, int, int, int);
-void stmgcn_seqsum_permute_bwd(void*, int, const void*, void*, int, int, int, int);
-void stmgcn_gate_fwd(void*, int, const void*, const void*, const void*,
-                     const void*, const void*, float*, float*, float*, void*,
-                     int, int, int, int);
-void stmgcn_gate_bwd(void*, int, const void*, const void*, const void*,
-                     const float*, const float*, const float*, float*, float*,
-                     float*, void*, void*, int, int, int, int);
-void stmgcn_head_fwd(void*, int, const void*, const void*, const void*,
-                     const void*, const void*, void*, void*, int, long);
-void stmgcn_head_bwd(void*, int, const void*, const void*, void*, int, long);
-void stmgcn_head_wgrad(void*, int, const void*, const void*, float*, float*,
-                       int, long);
-void stmgcn_mse_fwd(void*, int, const void*, const void*, float*, void*, long);
-void stmgcn_mse_bwd(void*, int, const void*, const float*, void*, long);
-void stmgcn_adam(void*, int, float*, void*, const void*, float*, float*,
-                 float*, long);
-void stmgcn_gather_grads(void*, int, const void**, const long*, const int*,
-                         int, void*);
-}
 
 at::Tensor seqsum_permute(at::Tensor obs) {
   TORCH_CHECK(obs.is_cuda() && obs.dim() == 4 && obs.is_contiguous());

@@ -4,6 +4,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include "kernels.h"  // entry-point prototypes, argument structs, SEQ_TILE
+
 #define STM_WAVE 64  // CDNA wavefront width (never 32)
 
 // dtype codes shared with the python side
@@ -62,7 +64,7 @@ __device__ __forceinline__ int lds_swz(int s, int cbyte) {
 //   store, and the wgrad lane (l16, lgrp) of gate g loads its A-fragment as
 //   the 16 B at k' = 8*lgrp. The permutation rho of the reduction index is
 //   free as long as the B operand (h_{t-1} / layer input rows) uses it too.
-#define SEQ_TILE 32   // sequences per RNN workgroup tile == dA tile rows
+// SEQ_TILE (kernels.h): sequences per RNN workgroup tile == dA tile rows
 #define STM_DA_GATES 256                          // 4H, H = 64
 #define STM_DA_TILE_ELEMS (SEQ_TILE * STM_DA_GATES)
 static_assert(SEQ_TILE == 32, "dA tile layout (rho) is defined for 32-row tiles");

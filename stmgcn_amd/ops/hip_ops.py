@@ -100,28 +100,23 @@ class ChebGconvFn(torch.autograd.Function):
         ctx.act = activation
         ctx.has_b = b is not None
         ctx.cin = Cin
-        if fused and csr.kind == "dual":
-            gb = csr.dual
-            outs = C.dual_gconv_fused_fwd(
-                x, csr.row_ptr, csr.col_idx, csr.vals,
-                gb.row_ptr, gb.col_idx, gb.vals, Wd,
-                b.to(x.dtype).contiguous() if b is not None else None,
-                gb.K_supports - 1, 1 if activation == "relu" else 0, training)
-            y = outs[0]
-            # outs[1:] = pf_1..pf_K, pb_1..pb_K
-            ctx.save_for_backward(x, Wd, W,
-                                  y if activation == "relu" else None,
-                                  *outs[1:])
-            return y
         if fused:
-            outs = C.cheb_gconv_fused_fwd(
-                x, csr.row_ptr, csr.col_idx, csr.vals, Wd,
-                b.to(x.dtype).contiguous() if b is not None else None,
-                csr.K_supports, csr.kind == "single",
-                1 if activation == "relu" else 0, training)
+            bd = b.to(x.dtype).contiguous() if b is not None else None
+            act = 1 if activation == "relu" else 0
+            if csr.kind == "dual":
+                gb = csr.dual
+                outs = C.dual_gconv_fused_fwd(
+                    x, csr.row_ptr, csr.col_idx, csr.vals,
+                    gb.row_ptr, gb.col_idx, gb.vals, Wd, bd,
+                    gb.K_supports - 1, act, training)
+            else:
+                outs = C.cheb_gconv_fused_fwd(
+                    x, csr.row_ptr, csr.col_idx, csr.vals, Wd, bd,
+                    csr.K_supports, csr.kind == "single", act, training)
             y = outs[0]
-            # outs[1:] = recurrence states p_1..p_{K_s-1} (p_0 == x), kept
-            # for the wgrad — their HBM writes were mandatory regardless
+            # outs[1:] = the recurrence states, kept for the wgrad (their HBM
+            # writes were mandatory regardless): p_1..p_{K_s-1} (p_0 == x), or
+            # pf_1..pf_K, pb_1..pb_K for dual
             ctx.save_for_backward(x, Wd, W,
                                   y if activation == "relu" else None,
                                   *outs[1:])
@@ -152,48 +147,41 @@ class ChebGconvFn(torch.autograd.Function):
         csr: CSRSupport = ctx.csr
         if ctx.fused:
             x, Wd, W, y = ctx.saved_tensors[:4]
-            ps = ctx.saved_tensors[4:]       # p_1..p_{K_s-1} from forward
+            ps = ctx.saved_tensors[4:]       # recurrence states from forward
             if ctx.act == "relu":
                 dz = (dy * (y > 0).to(dy.dtype)).contiguous()
             else:
                 dz = dy.contiguous()
-            single = csr.kind == "single"
+            dual, single = csr.kind == "dual", csr.kind == "single"
             K_s = csr.K_supports
             Cin, Cout = ctx.cin, dz.shape[-1]
-            if csr.kind == "dual":
+            if dual:
                 gb = csr.dual
                 K = gb.K_supports - 1
                 dX = C.dual_gconv_fused_bwd_dx(
                     dz, Wd, csr.row_ptr_t, csr.col_idx_t, csr.vals_t,
                     gb.row_ptr_t, gb.col_idx_t, gb.vals_t, K)
-                dWf = torch.zeros(K_s * Cin, Cout, dtype=torch.float32,
-                                  device=dz.device)
-                db_f = (torch.zeros(Cout, dtype=torch.float32,
-                                    device=dz.device) if ctx.has_b else None)
-                dz2 = dz.reshape(-1, Cout)
-                flat = [p.reshape(-1, Cin) for p in (x,) + tuple(ps)]
-                # rows [0,(K+1)Cin): x, pf_1..pf_K (+ db); rest: pb_1..pb_K
-                C.atb_wgrad_multi(flat[:K + 1], dz2, dWf[:(K + 1) * Cin], db_f)
-                C.atb_wgrad_multi(flat[K + 1:], dz2, dWf[(K + 1) * Cin:], None)
-                return (dX, dWf.to(W.dtype),
-                        db_f.to(W.dtype) if ctx.has_b else None,
-                        None, None, None)
-            dX = C.cheb_gconv_fused_bwd_dx(dz, Wd, csr.row_ptr_t,
-                                           csr.col_idx_t, csr.vals_t, K_s,
-                                           single)
-            # ---- dW/db: ONE multi-source MFMA reduction over the saved
-            # recurrence states (dz streamed once, no concat stack)
+            else:
+                dX = C.cheb_gconv_fused_bwd_dx(dz, Wd, csr.row_ptr_t,
+                                               csr.col_idx_t, csr.vals_t, K_s,
+                                               single)
+            # ---- dW/db: multi-source MFMA reductions over the saved
+            # recurrence states (no concat stack), <= 4 sources per launch
             dWf = torch.zeros(K_s * Cin, Cout, dtype=torch.float32,
                               device=dz.device)
             db_f = (torch.zeros(Cout, dtype=torch.float32, device=dz.device)
                     if ctx.has_b else None)
             dz2 = dz.reshape(-1, Cout)
-            srcs = [p.reshape(-1, Cin) for p in ps] if single \
-                else [x.reshape(-1, Cin)] + [p.reshape(-1, Cin) for p in ps]
-            C.atb_wgrad_multi(srcs, dz2, dWf, db_f)
-            dW = dWf.to(W.dtype)
-            db = db_f.to(W.dtype) if ctx.has_b else None
-            return dX, dW, db, None, None, None
+            srcs = [p.reshape(-1, Cin)
+                    for p in (ps if single else (x,) + tuple(ps))]
+            if dual:
+                # rows [0,(K+1)Cin): x, pf_1..pf_K (+ db); rest: pb_1..pb_K
+                C.atb_wgrad_multi(srcs[:K + 1], dz2, dWf[:(K + 1) * Cin], db_f)
+                C.atb_wgrad_multi(srcs[K + 1:], dz2, dWf[(K + 1) * Cin:], None)
+            else:
+                C.atb_wgrad_multi(srcs, dz2, dWf, db_f)   # dz streamed once
+            return (dX, dWf.to(W.dtype),
+                    db_f.to(W.dtype) if ctx.has_b else None, None, None, None)
 
         feat, W, y = ctx.saved_tensors
         if ctx.act == "relu":

@@ -141,3 +141,62 @@ def test_atb_wgrad_multi_empty_tail_chunks(nsrc, CA, N, dtype):
     """65537 rows -> 512 chunks of 129 rows: chunks 509..511 start past the
     end and must add nothing."""
     _check_atb_multi(nsrc, CA, N, 65537, dtype)
+
+
+# ---- the binding boundary: CSR validation, bias lifetime --------------------
+def test_csr_validation_at_every_binding():
+    """Every binding that takes a CSR refuses one whose rowptr is not N + 1
+    long or whose vals and colidx differ in length, before it launches. Both
+    malformed inputs only append an entry, so nothing indexes past valid data
+    even without the check."""
+    from stmgcn_amd.ops.functional import require_hip
+    _C = require_hip()
+    csr = lo.csr_graph(n=5, K=2).to(DEV)
+    K_s = csr.K_supports
+    g = lo._gen("csr-validation")
+    x = torch.randn(1, 5, 8, generator=g).to(DEV)
+    W = torch.randn(K_s * 8, 8, generator=g).to(DEV)
+    U = torch.randn(1, 5, K_s, 8, generator=g).to(DEV)
+    calls = {
+        "cheb_apply": lambda rp, ci, v: _C.cheb_apply(x, rp, ci, v, K_s, False),
+        "cheb_combine": lambda rp, ci, v: _C.cheb_combine(U, rp, ci, v, False),
+        "cheb_gconv_fused_fwd": lambda rp, ci, v: _C.cheb_gconv_fused_fwd(
+            x, rp, ci, v, W, None, K_s, False, 0, False),
+        "cheb_gconv_fused_bwd_dx": lambda rp, ci, v: _C.cheb_gconv_fused_bwd_dx(
+            x, W, rp, ci, v, K_s, False),
+        "spmm_axpby": lambda rp, ci, v: _C.spmm_axpby(x, None, rp, ci, v, 1.0, 0.0),
+    }
+    rp, ci, v = csr.row_ptr, csr.col_idx, csr.vals
+    long_rp = torch.cat([rp, rp[-1:]])
+    long_v = torch.cat([v, v[-1:]])
+    for name, call in calls.items():
+        call(rp, ci, v)                       # the call itself is well-formed
+        with pytest.raises(RuntimeError):
+            call(long_rp, ci, v)
+        with pytest.raises(RuntimeError):
+            call(rp, ci, long_v)
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("N,B,C,Cout", [(5, 1, 8, 8), (33, 2, 64, 64)])
+def test_fused_fwd_noncontiguous_bias(N, B, C, Cout):
+    """A strided bias view is made contiguous inside the binding; that copy
+    must outlive the launches. At the small shape y is allocated from the
+    block a freed copy would have returned to the allocator."""
+    from stmgcn_amd.ops.functional import require_hip
+    _C = require_hip()
+    csr = lo.csr_graph(n=N, K=2).to(DEV)
+    K_s = csr.K_supports
+    g = lo._gen("strided-bias", N, B, C, Cout)
+    x = torch.randn(B, N, C, generator=g).to(lo.BF16).to(DEV)
+    W = (torch.randn(K_s * C, Cout, generator=g) * 0.1).to(lo.BF16).to(DEV)
+    full = torch.randn(2 * Cout, generator=g).to(lo.BF16).to(DEV)
+    bias = full[::2]
+    assert not bias.is_contiguous()
+
+    def fwd(b):
+        return _C.cheb_gconv_fused_fwd(x, csr.row_ptr, csr.col_idx, csr.vals, W,
+                                       b, K_s, False, 1, False)[0]
+    y_strided = fwd(bias)
+    y_contig = fwd(bias.contiguous())
+    assert torch.equal(y_strided, y_contig)

@@ -171,3 +171,37 @@ def test_model_fp32_gpu_vs_cpu(monkeypatch):
     y_cpu = model(x, csr)
     y_gpu = model.to(DEV)(x.to(DEV), [c.to(DEV) for c in csr])
     torch.testing.assert_close(y_gpu.cpu(), y_cpu, rtol=1e-4, atol=1e-4)
+
+
+def test_csr_validation_at_dual_bindings():
+    """Both dual bindings refuse, for either generator, a rowptr that is not
+    N + 1 long and a vals longer than colidx, before they launch. Both
+    malformed inputs only append an entry: nothing would index past valid
+    data even without the check."""
+    from stmgcn_amd.ops.functional import require_hip
+    _C = require_hip()
+    csr = do.dual_graph(5, 2).to(DEV)
+    gb = csr.dual
+    K = gb.K_supports - 1
+    g = lo._gen("dual-csr-validation")
+    x = torch.randn(1, 5, 8, generator=g).to(lo.BF16).to(DEV)
+    W = torch.randn(csr.K_supports * 8, 8, generator=g).to(lo.BF16).to(DEV)
+    fwd_csr = [csr.row_ptr, csr.col_idx, csr.vals, gb.row_ptr, gb.col_idx, gb.vals]
+    bwd_csr = [csr.row_ptr_t, csr.col_idx_t, csr.vals_t,
+               gb.row_ptr_t, gb.col_idx_t, gb.vals_t]
+    calls = [
+        (fwd_csr, lambda c: _C.dual_gconv_fused_fwd(x, *c, W, None, K, 0, False)),
+        (bwd_csr, lambda c: _C.dual_gconv_fused_bwd_dx(x, W, *c, K)),
+    ]
+    for good, call in calls:
+        call(good)                            # the call itself is well-formed
+        for d in (0, 3):                      # forward / backward generator
+            long_rp = list(good)
+            long_rp[d] = torch.cat([good[d], good[d][-1:]])
+            with pytest.raises(RuntimeError):
+                call(long_rp)
+            long_v = list(good)
+            long_v[d + 2] = torch.cat([good[d + 2], good[d + 2][-1:]])
+            with pytest.raises(RuntimeError):
+                call(long_v)
+    torch.cuda.synchronize()
