@@ -526,6 +526,86 @@ std::vector<at::Tensor> lstm_wgrad(at::Tensor dA, at::Tensor hseq, at::Tensor x)
   return {dwih, dwhh, db};
 }
 
+// Finishing form of lstm_wgrad: the same launch, and its last workgroup per
+// layer writes the gradients in the activations' dtype and in their final
+// shapes. Returns [dw_ih_0, dw_hh_0, db_ih_0, db_hh_0, dw_ih_1, ...]: contiguous
+// views of ONE flat buffer. One zero fill covers sums and tickets.
+std::vector<at::Tensor> lstm_wgrad_grads(at::Tensor dA, at::Tensor hseq,
+                                         at::Tensor x, bool gru) {
+  TORCH_CHECK(dA.is_cuda() && dA.dim() == 4 && dA.is_contiguous());
+  TORCH_CHECK(hseq.is_cuda() && x.is_cuda());
+  TORCH_CHECK(hseq.is_contiguous() && x.is_contiguous() && x.dim() == 3);
+  TORCH_CHECK(hseq.scalar_type() == dA.scalar_type() &&
+              x.scalar_type() == dA.scalar_type());
+  const int L = dA.size(0), Tst = dA.size(1);
+  const long S_pad = dA.size(2);
+  const long R = (long)Tst * S_pad;
+  const int S = x.size(0), cin = x.size(2);
+  TORCH_CHECK(L >= 1 && L <= 8 && (cin == 1 || cin == kH));
+  TORCH_CHECK(dA.size(3) == 4 * kH && S_pad % SEQ_TILE == 0 && S <= S_pad,
+              "dA must be (L, Tst, S_pad, 4H) with S_pad a multiple of 32");
+  TORCH_CHECK(hseq.dim() == 4 && hseq.size(0) == L && hseq.size(1) == Tst &&
+              hseq.size(2) == S_pad && hseq.size(3) == kH && x.size(1) == Tst);
+  const long n_w = (long)L * 4 * kH * kH, n_b = (long)L * 4 * kH;
+  auto ws = at::zeros({2 * n_w + n_b + 8}, dA.options().dtype(at::kFloat));
+  float* wp = ws.data_ptr<float>();
+  const long GH = (gru ? 3 : 4) * kH;
+  const long total = GH * (cin + kH + 2) + (long)(L - 1) * GH * (2 * kH + 2);
+  auto flat = at::empty({total}, dA.options());
+  stmgcn_lstm_wgrad_grads(stream(), dtype_code(dA), dA.data_ptr(), hseq.data_ptr(),
+                          x.data_ptr(), wp, wp + n_w, wp + 2 * n_w,
+                          (unsigned*)(wp + 2 * n_w + n_b), flat.data_ptr(), R,
+                          S_pad, S, Tst, L, cin, gru ? 1 : 0);
+  std::vector<at::Tensor> out;
+  long off = 0;
+  for (int l = 0; l < L; ++l) {
+    const long cl = l == 0 ? cin : kH;
+    out.push_back(flat.narrow(0, off, GH * cl).view({GH, cl})); off += GH * cl;
+    out.push_back(flat.narrow(0, off, GH * kH).view({GH, kH})); off += GH * kH;
+    out.push_back(flat.narrow(0, off, GH)); off += GH;
+    out.push_back(flat.narrow(0, off, GH)); off += GH;
+  }
+  return out;
+}
+
+// W_ih^T / W_hh^T of every layer (the operands lstm_bwd reads) in ONE launch
+// into one buffer: returns [w_ihT_0.., w_hhT_0..] as views of it.
+std::vector<at::Tensor> lstm_pack_bwd_weights(std::vector<at::Tensor> w_ih,
+                                              std::vector<at::Tensor> w_hh) {
+  const int L = (int)w_ih.size();
+  TORCH_CHECK(L >= 1 && L <= 8 && (int)w_hh.size() == L);
+  const auto dt = w_ih[0].scalar_type();
+  TORCH_CHECK(dt == at::kBFloat16 || dt == at::kHalf);
+  const int cin = w_ih[0].size(1);
+  TORCH_CHECK(cin == 1 || cin == kH);
+  const void *wi[8], *wh[8];
+  for (int l = 0; l < L; ++l) {
+    TORCH_CHECK(w_ih[l].is_cuda() && w_hh[l].is_cuda() && w_ih[l].is_contiguous() &&
+                w_hh[l].is_contiguous() && w_ih[l].scalar_type() == dt &&
+                w_hh[l].scalar_type() == dt);
+    TORCH_CHECK(w_ih[l].dim() == 2 && w_ih[l].size(0) == 4 * kH &&
+                w_ih[l].size(1) == (l == 0 ? cin : kH));
+    TORCH_CHECK(w_hh[l].dim() == 2 && w_hh[l].size(0) == 4 * kH &&
+                w_hh[l].size(1) == kH);
+    wi[l] = w_ih[l].data_ptr(); wh[l] = w_hh[l].data_ptr();
+  }
+  const long total = 4L * kH * (cin + (long)(L - 1) * kH + (long)L * kH);
+  auto flat = at::empty({total}, w_ih[0].options());
+  stmgcn_lstm_pack_bwd_weights(stream(), wi, wh, L, cin, flat.data_ptr());
+  std::vector<at::Tensor> out;
+  long off = 0;
+  for (int l = 0; l < L; ++l) {
+    const long cl = l == 0 ? cin : kH;
+    out.push_back(flat.narrow(0, off, 4 * kH * cl).view({cl, 4 * kH}));
+    off += 4 * kH * cl;
+  }
+  for (int l = 0; l < L; ++l) {
+    out.push_back(flat.narrow(0, off, 4L * kH * kH).view({kH, 4 * kH}));
+    off += 4L * kH * kH;
+  }
+  return out;
+}
+
 // C = A^T @ B (+ db = colsum(B)) for tall-skinny wgrads (M<=256, N<=64).
 std::vector<at::Tensor> atb_wgrad(at::Tensor A, at::Tensor B, bool want_db) {
   TORCH_CHECK(A.is_cuda() && A.dim() == 2 && B.dim() == 2);
@@ -586,6 +666,61 @@ void atb_wgrad_multi(std::vector<at::Tensor> As, at::Tensor B, at::Tensor C,
                          B.data_ptr(), C.data_ptr<float>(), dbp, rows, N);
 }
 
+// Finishing form of atb_wgrad_multi: returns dW (len(As)*CA, N) and, with
+// want_db, db (N,) in the dtype of B. As[:split] (<= 4, with db) and As[split:]
+// (<= 4) are one launch each over one zero-filled fp32 workspace of sums and
+// tickets; each launch's last workgroup rounds its own rows.
+std::vector<at::Tensor> atb_wgrad_multi_grads(std::vector<at::Tensor> As,
+                                              at::Tensor B, int64_t split,
+                                              bool want_db) {
+  const int nsrc = (int)As.size();
+  TORCH_CHECK(nsrc >= 1 && split >= 1 && split <= 4 && split <= nsrc &&
+              nsrc - split <= 4);
+  TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dim() == 2);
+  const long rows = B.size(0);
+  const int CA = As[0].size(1), N = B.size(1);
+  TORCH_CHECK(4 * CA <= 256 && N <= 64 && CA % 8 == 0 && N % 8 == 0);
+  const void* srcs[8];
+  for (int i = 0; i < nsrc; ++i) {
+    TORCH_CHECK(As[i].is_cuda() && As[i].is_contiguous() && As[i].dim() == 2 &&
+                As[i].size(0) == rows && As[i].size(1) == CA &&
+                As[i].scalar_type() == B.scalar_type());
+    srcs[i] = As[i].data_ptr();
+  }
+  const long nW = (long)nsrc * CA * N;
+  auto ws = at::zeros({nW + N + 8}, B.options().dtype(at::kFloat));
+  float* wp = ws.data_ptr<float>();
+  unsigned* tickets = (unsigned*)(wp + nW + N);
+  auto dW = at::empty({(long)nsrc * CA, (long)N}, B.options());
+  at::Tensor db;
+  if (want_db) db = at::empty({N}, B.options());
+  const int dt = dtype_code(B);
+  const long es = B.element_size();
+  stmgcn_atb_wgrad_multi_grads(stream(), dt, srcs, (int)split, CA, B.data_ptr(), wp,
+                               want_db ? wp + nW : nullptr, tickets, dW.data_ptr(),
+                               want_db ? db.data_ptr() : nullptr, rows, N);
+  if (split < nsrc) {
+    const long r0 = split * CA * (long)N;
+    stmgcn_atb_wgrad_multi_grads(stream(), dt, srcs + split, nsrc - (int)split, CA,
+                                 B.data_ptr(), wp + r0, nullptr, tickets + 1,
+                                 (char*)dW.data_ptr() + r0 * es, nullptr, rows, N);
+  }
+  return want_db ? std::vector<at::Tensor>{dW, db} : std::vector<at::Tensor>{dW};
+}
+
+// dz = dy * (y > 0) in one launch (the ReLU mask of the gconv backward)
+at::Tensor relu_bwd(at::Tensor dy, at::Tensor y) {
+  TORCH_CHECK(dy.is_cuda() && y.is_cuda() && dy.sizes() == y.sizes() &&
+              dy.scalar_type() == y.scalar_type());
+  TORCH_CHECK(dy.scalar_type() == at::kBFloat16 || dy.scalar_type() == at::kHalf,
+              "relu_bwd serves bf16/f16");
+  dy = dy.contiguous(); y = y.contiguous();
+  auto dz = at::empty_like(dy);
+  stmgcn_relu_bwd(stream(), dtype_code(dy), dy.data_ptr(), y.data_ptr(),
+                  dz.data_ptr(), dy.numel());
+  return dz;
+}
+
 at::Tensor mfma_probe(at::Tensor A, at::Tensor B) {
   TORCH_CHECK(A.is_cuda() && A.scalar_type() == at::kBFloat16);
   auto D = at::empty({16, 16}, A.options().dtype(at::kFloat));
@@ -616,41 +751,77 @@ at::Tensor seqsum_permute_bwd(at::Tensor dxs, int64_t C) {
   return dobs;
 }
 
+// node_major: out is (B,N,T,C) — the sequence-major layout the RNN consumes —
+// instead of (B,T,N,C). z is the pooled mean (fp32) either way.
 std::vector<at::Tensor> gate_fwd(at::Tensor obs, at::Tensor g, at::Tensor xs,
-                                 at::Tensor fcw, at::Tensor fcb) {
+                                 at::Tensor fcw, at::Tensor fcb, bool node_major) {
   TORCH_CHECK(obs.is_cuda() && obs.dim() == 4 && obs.is_contiguous());
   const int B = obs.size(0), Tst = obs.size(1), N = obs.size(2), C = obs.size(3);
   TORCH_CHECK(Tst <= 16, "gate kernel serves T <= 16");
+  TORCH_CHECK(g.numel() == (long)B * N * Tst && xs.numel() == g.numel() &&
+              fcw.numel() == Tst * Tst && fcb.numel() == Tst);
+  TORCH_CHECK(g.is_cuda() && xs.is_cuda() && fcw.is_cuda() && fcb.is_cuda());
+  TORCH_CHECK(g.scalar_type() == obs.scalar_type() &&
+              xs.scalar_type() == obs.scalar_type() &&
+              fcw.scalar_type() == obs.scalar_type() &&
+              fcb.scalar_type() == obs.scalar_type());
   auto fopt = obs.options().dtype(at::kFloat);
-  // z doubles as the multi-block zsum atomic target -> zeroed
-  auto z = at::zeros({B, Tst}, fopt), u = at::empty({B, Tst}, fopt),
-       s = at::empty({B, Tst}, fopt);
-  auto out = at::empty_like(obs);
-  stmgcn_gate_fwd(stream(), dtype_code(obs), g.contiguous().data_ptr(),
-                  xs.contiguous().data_ptr(), fcw.contiguous().data_ptr(),
-                  fcb.contiguous().data_ptr(), obs.data_ptr(),
-                  z.data_ptr<float>(), u.data_ptr<float>(), s.data_ptr<float>(),
-                  out.data_ptr(), B, Tst, N, C);
+  // z doubles as the multi-block zsum atomic target, followed by one arrival
+  // ticket per batch row -> one zero fill for both
+  auto zt = at::zeros({(long)B * Tst + B}, fopt);
+  auto z = zt.narrow(0, 0, (long)B * Tst).view({B, Tst});
+  auto u = at::empty({B, Tst}, fopt), s = at::empty({B, Tst}, fopt);
+  auto out = node_major ? at::empty({B, N, Tst, C}, obs.options())
+                        : at::empty_like(obs);
+  auto gc = g.contiguous(), xc = xs.contiguous(), wc = fcw.contiguous(),
+       bc = fcb.contiguous();
+  stmgcn_gate_fwd(stream(), dtype_code(obs), gc.data_ptr(), xc.data_ptr(),
+                  wc.data_ptr(), bc.data_ptr(), obs.data_ptr(),
+                  zt.data_ptr<float>(), u.data_ptr<float>(), s.data_ptr<float>(),
+                  (unsigned*)(zt.data_ptr<float>() + (long)B * Tst),
+                  out.data_ptr(), B, Tst, N, C, node_major ? 1 : 0);
   return {out, z, u, s};
 }
 
+// Returns {dobs (undefined without want_dobs), dg, dw (T,T), db (T,), dw fp32,
+// db fp32}: dw/db are summed over the batch in-kernel, in the dtype of obs and
+// in fp32. node_major: dout is (B,N,T,C).
 std::vector<at::Tensor> gate_bwd(at::Tensor dout, at::Tensor obs, at::Tensor fcw,
-                                 at::Tensor z, at::Tensor u, at::Tensor s) {
+                                 at::Tensor z, at::Tensor u, at::Tensor s,
+                                 bool node_major, bool want_dobs) {
   dout = dout.contiguous();
+  TORCH_CHECK(obs.is_cuda() && obs.dim() == 4 && obs.is_contiguous());
   const int B = obs.size(0), Tst = obs.size(1), N = obs.size(2), C = obs.size(3);
+  TORCH_CHECK(dout.is_cuda() && fcw.is_cuda() && z.is_cuda() && u.is_cuda() &&
+              s.is_cuda() && z.scalar_type() == at::kFloat &&
+              u.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat);
+  TORCH_CHECK(Tst <= 16 && dout.numel() == obs.numel() &&
+              dout.scalar_type() == obs.scalar_type() &&
+              fcw.scalar_type() == obs.scalar_type() && fcw.numel() == Tst * Tst);
+  TORCH_CHECK(z.is_contiguous() && u.is_contiguous() && s.is_contiguous() &&
+              z.numel() == (long)B * Tst && u.numel() == z.numel() &&
+              s.numel() == z.numel());
   auto fopt = obs.options().dtype(at::kFloat);
-  // dz doubles as the multi-block ds atomic target -> zeroed
-  auto dz = at::zeros({B, Tst}, fopt);
+  // dz doubles as the multi-block ds atomic target, followed by the B + 1
+  // arrival tickets -> one zero fill for both
+  auto dzt = at::zeros({(long)B * Tst + B + 1}, fopt);
   auto dw_part = at::empty({B, Tst, Tst}, fopt);
   auto db_part = at::empty({B, Tst}, fopt);
-  auto dobs = at::empty_like(obs);
+  auto dw_f = at::empty({Tst, Tst}, fopt), db_f = at::empty({Tst}, fopt);
+  auto dw = at::empty({Tst, Tst}, obs.options()), db = at::empty({Tst}, obs.options());
+  at::Tensor dobs;
+  if (want_dobs) dobs = at::empty_like(obs);
   auto dg = at::empty({B, N, Tst}, obs.options());
+  auto wc = fcw.contiguous();
   stmgcn_gate_bwd(stream(), dtype_code(obs), dout.data_ptr(), obs.data_ptr(),
-                  fcw.contiguous().data_ptr(), z.data_ptr<float>(),
-                  u.data_ptr<float>(), s.data_ptr<float>(), dz.data_ptr<float>(),
+                  wc.data_ptr(), z.data_ptr<float>(), u.data_ptr<float>(),
+                  s.data_ptr<float>(), dzt.data_ptr<float>(),
                   dw_part.data_ptr<float>(), db_part.data_ptr<float>(),
-                  dobs.data_ptr(), dg.data_ptr(), B, Tst, N, C);
-  return {dobs, dg, dw_part, db_part};
+                  (unsigned*)(dzt.data_ptr<float>() + (long)B * Tst),
+                  dw_f.data_ptr<float>(), db_f.data_ptr<float>(), dw.data_ptr(),
+                  db.data_ptr(), want_dobs ? dobs.data_ptr() : nullptr,
+                  dg.data_ptr(), B, Tst, N, C, node_major ? 1 : 0);
+  return {dobs, dg, dw, db, dw_f, db_f};
 }
 
 std::vector<at::Tensor> head_fwd(std::vector<at::Tensor> feats, at::Tensor w,
@@ -691,6 +862,26 @@ std::vector<at::Tensor> head_wgrad(at::Tensor dy, at::Tensor fsum) {
   auto db = at::zeros({1}, fopt);
   stmgcn_head_wgrad(stream(), dtype_code(dy), dy.data_ptr(), fsum.data_ptr(),
                     dw.data_ptr<float>(), db.data_ptr<float>(), G, BN);
+  return {dw, db};
+}
+
+// Finishing form: dw (1, G) and db (1,) in the dtype of dy from one zero-filled
+// fp32 workspace (sums + ticket); the kernel's last workgroup rounds them.
+std::vector<at::Tensor> head_wgrad_grads(at::Tensor dy, at::Tensor fsum) {
+  dy = dy.contiguous();
+  fsum = fsum.contiguous();
+  TORCH_CHECK(fsum.is_cuda() && dy.is_cuda() && fsum.dim() == 3 &&
+              dy.scalar_type() == fsum.scalar_type());
+  const long BN = (long)fsum.size(0) * fsum.size(1);
+  const int G = fsum.size(2);
+  TORCH_CHECK(G <= 64 && dy.numel() == BN);
+  auto ws = at::zeros({64 + 8}, dy.options().dtype(at::kFloat));
+  float* wp = ws.data_ptr<float>();
+  auto dw = at::empty({1, G}, dy.options());
+  auto db = at::empty({1}, dy.options());
+  stmgcn_head_wgrad_grads(stream(), dtype_code(dy), dy.data_ptr(), fsum.data_ptr(),
+                          wp, wp + 64, (unsigned*)(wp + 68), dw.data_ptr(),
+                          db.data_ptr(), G, BN);
   return {dw, db};
 }
 
@@ -751,12 +942,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_fwd", &lstm_fwd, "Fused multi-layer LSTM forward (persistent)");
   m.def("lstm_bwd", &lstm_bwd, "Fused LSTM dgrad (BPTT in-kernel)");
   m.def("lstm_wgrad", &lstm_wgrad, "All-layer LSTM weight grads, one launch");
+  m.def("lstm_wgrad_grads", &lstm_wgrad_grads,
+        "All-layer LSTM/GRU weight grads, finished in-kernel: final dtype/shapes");
+  m.def("lstm_pack_bwd_weights", &lstm_pack_bwd_weights,
+        "W_ih^T / W_hh^T of every layer in one launch (lstm_bwd operands)");
+  m.def("atb_wgrad_multi_grads", &atb_wgrad_multi_grads,
+        "All-support wgrad finished in-kernel: dW / db in the parameter dtype");
+  m.def("relu_bwd", &relu_bwd, "dz = dy * (y > 0)");
+  m.def("head_wgrad_grads", &head_wgrad_grads,
+        "K7: dw/db reduction finished in-kernel (parameter dtype)");
   m.def("atb_wgrad", &atb_wgrad, "C = A^T B reduction GEMM (+colsum(B))");
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA fragment-layout probe");
   m.def("seqsum_permute", &seqsum_permute, "K3: feature-sum + transpose");
   m.def("seqsum_permute_bwd", &seqsum_permute_bwd);
-  m.def("gate_fwd", &gate_fwd, "K4: fused contextual gate forward");
-  m.def("gate_bwd", &gate_bwd, "K4: fused contextual gate backward");
+  m.def("gate_fwd", &gate_fwd, "K4: fused contextual gate forward",
+        py::arg("obs"), py::arg("g"), py::arg("xs"), py::arg("fcw"),
+        py::arg("fcb"), py::arg("node_major") = false);
+  m.def("gate_bwd", &gate_bwd, "K4: fused contextual gate backward",
+        py::arg("dout"), py::arg("obs"), py::arg("fcw"), py::arg("z"),
+        py::arg("u"), py::arg("s"), py::arg("node_major") = false,
+        py::arg("want_dobs") = true);
   m.def("head_fwd", &head_fwd, "K7: branch-sum + FC head forward");
   m.def("head_bwd", &head_bwd, "K7: head backward (dfeat)");
   m.def("head_wgrad", &head_wgrad, "K7: dw/db reduction (no library GEMM)");

@@ -88,6 +88,57 @@ static_assert(stm_da_rho(0) == 0 && stm_da_rho(4) == 16 && stm_da_rho(8) == 4 &&
               stm_da_rho(31) == 31 && stm_da_rho_inv(stm_da_rho(13)) == 13 &&
               stm_da_rho_inv(stm_da_rho(22)) == 22, "rho / rho_inv mismatch");
 
+// ---------------------------------------------------------------------------
+// "Last arriver finishes": in-launch hand-off for the reduction kernels that
+// accumulate fp32 partials with unsafeAtomicAdd. Every workgroup of a slice
+// calls this once, after its atomics; the call returns true (workgroup-
+// uniform) in exactly one of them — the one that drew the last of `expected`
+// tickets — and by then every workgroup's partials are visible to plain
+// vector loads of all its waves. That workgroup rounds the sums to the
+// parameter dtype and writes the gradients in their final shapes, so no
+// separate convert / slice / reduce launch follows the kernel.
+//
+// Arrival: every wave drains its atomics (vmcnt), the workgroup meets, lane 0
+// releases at agent scope, drains again (the fence's own wait is not relied
+// on) and only then draws its ticket with a relaxed agent-scope add. The last
+// arriver acquires at agent scope once (drops this CU's stale L1 lines),
+// drains, and the closing barrier holds the other waves behind that. No
+// __threadfence() per thread, no workgroup-scope fence, no assumption on
+// dispatch order or placement; nobody spins, so nothing can hang.
+//
+// `ticket` must be zero at launch: it lives in the same zero-filled fp32
+// workspace as the accumulators (one fill clears both). `flag` is one int of
+// the caller's existing LDS array that no wave still reads.
+__device__ __forceinline__ bool stm_last_arriver(unsigned* ticket,
+                                                 unsigned expected, int* flag) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = (t + 1 == expected);
+    *flag = last ? 1 : 0;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  return *flag != 0;
+}
+
+// 4 fp32 sums -> 4 values of T, one 8-byte store (dst 8-byte aligned)
+template <typename T>
+__device__ __forceinline__ void stm_store4(T* dst, float a, float b, float c,
+                                           float d) {
+  union { T t[4]; uint2 u; } pk;
+  pk.t[0] = fromF<T>(a); pk.t[1] = fromF<T>(b);
+  pk.t[2] = fromF<T>(c); pk.t[3] = fromF<T>(d);
+  *(uint2*)dst = pk.u;
+}
+
 #define STM_CHECK_HIP(expr)                                                    \
   do {                                                                          \
     hipError_t _e = (expr);                                                     \

@@ -1101,3 +1101,53 @@ extern "C" void stmgcn_lstm_bwd(void* stream_v, int dtype, const void* dout,
     launch_bwd<__half>(stream, dout, x, cseq_g, gates_g, p, dx, dA_g, dh_g,
                        S, Tst, L, cin, ret_seq, gru);
 }
+
+// ===========================================================================
+// Backward weight operands, one launch: lstm_bwd_kernel reads W_ih^T
+// (cin_l, 4H) and W_hh^T (H, 4H) of every layer; this writes all 2L of them
+// into one buffer (dst offsets in elements), replacing one transpose-copy
+// launch per matrix. The weights change every step, so the transposes cannot
+// be kept across steps. Pure 2-byte moves: the same kernel serves bf16 / f16.
+// Grid (4 row tiles, 2L matrices), 256 threads; a 64 x 64 tile of the
+// (4H, cols) source goes through LDS so both sides stay coalesced.
+struct PackMats {
+  const unsigned short* src[2 * MAX_LAYERS];
+  long dst_off[2 * MAX_LAYERS];
+  int cols[2 * MAX_LAYERS];
+};
+
+__global__ void __launch_bounds__(256)
+lstm_pack_bwd_weights_kernel(PackMats pm, unsigned short* __restrict__ dst) {
+  __shared__ unsigned short tile[64][66];
+  const unsigned short* src = pm.src[blockIdx.y];
+  unsigned short* out = dst + pm.dst_off[blockIdx.y];
+  const int cols = pm.cols[blockIdx.y];     // 1 or 64
+  const int r0 = blockIdx.x * 64;           // of the 4H = 256 source rows
+  const int lo = threadIdx.x & 63, hi = threadIdx.x >> 6;
+  for (int r = hi; r < 64; r += 4)
+    if (lo < cols) tile[r][lo] = src[(long)(r0 + r) * cols + lo];
+  __syncthreads();
+  for (int c = hi; c < cols; c += 4)
+    out[(long)c * 256 + r0 + lo] = tile[lo][c];
+}
+
+extern "C" void stmgcn_lstm_pack_bwd_weights(void* stream, const void** w_ih,
+                                             const void** w_hh, int L, int cin,
+                                             void* dst) {
+  PackMats pm{};
+  long off = 0;
+  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {   // all W_ih^T, then all W_hh^T
+    pm.src[l] = (const unsigned short*)w_ih[l];
+    pm.cols[l] = l == 0 ? cin : 64;
+    pm.dst_off[l] = off;
+    off += 256L * pm.cols[l];
+  }
+  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
+    pm.src[L + l] = (const unsigned short*)w_hh[l];
+    pm.cols[L + l] = 64;
+    pm.dst_off[L + l] = off;
+    off += 256L * 64;
+  }
+  hipLaunchKernelGGL(lstm_pack_bwd_weights_kernel, dim3(4, 2 * L), dim3(256), 0,
+                     (hipStream_t)stream, pm, (unsigned short*)dst);
+}

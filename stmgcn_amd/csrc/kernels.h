@@ -82,13 +82,28 @@ void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout, const void* x,
     void* dx, void* dA_g, void* dh_g, int S, int Tst, int L, int cin, int ret_seq,
     int gru);
 void stmgcn_mfma_probe(void* stream, const void* A, const void* B, void* D);
+// W_ih^T (cin_l, 4H) of layers 0..L-1, then W_hh^T (H, 4H) of layers 0..L-1,
+// back to back in dst (2-byte elements), one launch
+void stmgcn_lstm_pack_bwd_weights(void* stream, const void** w_ih, const void** w_hh,
+    int L, int cin, void* dst);
 
 // ---- wgrad.hip ----
 void stmgcn_lstm_wgrad(void* stream, int dtype, const void* dA, const void* hseq,
     const void* x, float* dwih, float* dwhh, float* db, long R, long S_pad, int S,
     int Tst, int L, int cin);
+// finishing form: the last workgroup of each layer writes [dw_ih | dw_hh | db_ih |
+// db_hh] of that layer to `out` in `dtype`, final shapes, layers back to back;
+// dwih/dwhh/db/tickets are one zero-filled workspace (tickets: L words)
+void stmgcn_lstm_wgrad_grads(void* stream, int dtype, const void* dA, const void* hseq,
+    const void* x, float* dwih, float* dwhh, float* db, unsigned* tickets, void* out,
+    long R, long S_pad, int S, int Tst, int L, int cin, int gru);
 void stmgcn_atb_wgrad(void* stream, int dtype, const void* A, const void* B, float* C,
     float* db, long rows, int M, int N);
+// finishing form: the last workgroup writes dW (nsrc*CA, N) and dbo (N,) in `dtype`
+// from the zero-filled fp32 C / db / ticket workspace
+void stmgcn_atb_wgrad_multi_grads(void* stream, int dtype, const void** As, int nsrc,
+    int CA, const void* B, float* C, float* db, unsigned* ticket, void* dW, void* dbo,
+    long rows, int N);
 void stmgcn_atb_wgrad_multi(void* stream, int dtype, const void** As, int nsrc, int CA,
     const void* B, float* C, float* db, long rows, int N);
 
@@ -97,18 +112,27 @@ void stmgcn_seqsum_permute(void* stream, int dtype, const void* obs, void* out, 
     int Tst, int N, int C);
 void stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs, void* dobs,
     int B, int Tst, int N, int C);
+// z | tickets (B) and dz | tickets (B + 1) are each one zero-filled allocation;
+// node_major: out / dout are (B,N,T,C); dobs may be null; dw_f/db_f fp32, dw/db `dtype`
 void stmgcn_gate_fwd(void* stream, int dtype, const void* g, const void* xs,
     const void* fcw, const void* fcb, const void* obs, float* z, float* u, float* s,
-    void* out, int B, int Tst, int N, int C);
+    unsigned* tickets, void* out, int B, int Tst, int N, int C, int node_major);
 void stmgcn_gate_bwd(void* stream, int dtype, const void* dout, const void* obs,
     const void* fcw, const float* z, const float* u, const float* s, float* dz,
-    float* dw_part, float* db_part, void* dobs, void* dg, int B, int Tst, int N, int C);
+    float* dw_part, float* db_part, unsigned* tickets, float* dw_f, float* db_f,
+    void* dw, void* db, void* dobs, void* dg, int B, int Tst, int N, int C,
+    int node_major);
 void stmgcn_head_fwd(void* stream, int dtype, const void* f0, const void* f1,
     const void* f2, const void* w, const void* bias, void* y, void* fsum, int G, long BN);
 void stmgcn_head_bwd(void* stream, int dtype, const void* dy, const void* w, void* dfeat,
     int G, long BN);
 void stmgcn_head_wgrad(void* stream, int dtype, const void* dy, const void* fsum,
     float* dw, float* db, int G, long BN);
+void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy, const void* fsum,
+    float* dw, float* db, unsigned* ticket, void* dw_out, void* db_out, int G, long BN);
+// dz = dy * (y > 0), bf16/f16
+void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y, void* dz,
+    long n);
 void stmgcn_mse_fwd(void* stream, int dtype, const void* pred, const void* tgt,
     float* loss, void* diff, long n);
 void stmgcn_mse_bwd(void* stream, int dtype, const void* diff, const float* gscale,

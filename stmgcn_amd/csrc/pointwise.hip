@@ -4,8 +4,9 @@
 //      (reference STMGCN.py:36,39)
 //  K4  contextual gate: z = mean_n(gconv + x_seq); s = sigmoid(FC(relu(FC(z))))
 //      with ONE weight-tied FC applied twice (STMGCN.py:43, quirk 2);
-//      out = obs * s  (eqs. 6-9). Forward = one per-batch reduce+gate kernel
-//      + one broadcast-multiply; backward mirrors it.
+//      out = obs * s  (eqs. 6-9). Forward = one node-reduce kernel whose last
+//      workgroup per batch row runs the FC stages + one broadcast-multiply;
+//      backward mirrors it and also sums dw/db over the batch.
 //  K7  branch-fuse + FC head: y = (sum_m feats_m) @ W^T + b (STMGCN.py:116-118)
 //  K8  fused MSE loss + grad  (Model_Trainer.py:38)
 //  K9  multi-tensor Adam over a flat fp32 master arena with bf16/f16 working
@@ -53,15 +54,28 @@ __global__ void seqsum_permute_bwd_kernel(const T* __restrict__ dxs,  // (B,N,T)
   dobs[i] = dxs[(b * N + n) * (long)Tst + t];
 }
 
-// ---- K4 forward part A1: multi-block node reduce -> zsum (B,T) fp32 -------
+// ---- K4 forward part A: multi-block node reduce + tied double-FC ----------
 // grid (nchunks, B): scales to any N (the old one-block-per-batch form was
-// 3.5 ms/call at N=4096 — 16 blocks on 256 CUs).
+// 3.5 ms/call at N=4096 — 16 blocks on 256 CUs). The workgroups of batch row
+// b add their partial pooled sums to zsum[b] and arrive at ticket b
+// (stm_last_arriver, common.h); the last one of the row turns the sums into
+// z = mean, u = relu(W z + b), s = sigmoid(W u + b) — lane t of its first
+// wave owns output t, so the T x T products run T-wide instead of on one
+// serial thread per row in a launch of its own. z overwrites zsum in place.
 template <typename T>
 __global__ void gate_fwd_reduce_kernel(const T* __restrict__ g,     // (B,N,T)
                                        const T* __restrict__ xs,    // (B,N,T)
                                        float* __restrict__ zsum,    // (B,T) zeroed
+                                       const T* __restrict__ fcw,   // (T,T)
+                                       const T* __restrict__ fcb,   // (T,)
+                                       float* __restrict__ u_out,   // (B,T)
+                                       float* __restrict__ s_out,   // (B,T)
+                                       unsigned* tickets,           // (B,) zeroed
                                        int N, int Tst) {
   __shared__ float red[256];
+  // arrival flag: the last word of red (the reduce uses the first 4 *
+  // GATE_MAX_T words, the FC stage the first 2 * GATE_MAX_T)
+  int* last_flag = (int*)&red[255];
   const long b = blockIdx.y;
   const int nchunks = gridDim.x;
   const int chunk = (N + nchunks - 1) / nchunks;
@@ -87,52 +101,79 @@ __global__ void gate_fwd_reduce_kernel(const T* __restrict__ g,     // (B,N,T)
     }
     __syncthreads();
   }
-}
 
-// ---- K4 forward part A2: tiny per-batch tied double-FC --------------------
-template <typename T>
-__global__ void gate_fwd_fc_kernel(const float* __restrict__ zsum, // (B,T)
-                                   const T* __restrict__ fcw,      // (T,T)
-                                   const T* __restrict__ fcb,      // (T,)
-                                   float* __restrict__ z_out, float* __restrict__ u_out,
-                                   float* __restrict__ s_out, int N, int Tst, int B) {
-  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  float z[GATE_MAX_T], u[GATE_MAX_T];
-  for (int t = 0; t < Tst; ++t) z[t] = zsum[b * Tst + t] / (float)N;
-  for (int t = 0; t < Tst; ++t) {                  // u = relu(W z + b)
+  if (!stm_last_arriver(&tickets[b], gridDim.x, last_flag)) return;
+  float* zs = red;
+  float* us = red + GATE_MAX_T;
+  const int t = threadIdx.x;
+  if (t < Tst) zs[t] = zsum[b * Tst + t] / (float)N;
+  __syncthreads();
+  if (t < Tst) {                                   // u = relu(W z + b)
     float a = toF<T>(fcb[t]);
-    for (int j = 0; j < Tst; ++j) a += toF<T>(fcw[t * Tst + j]) * z[j];
-    u[t] = a > 0.f ? a : 0.f;
+    for (int j = 0; j < Tst; ++j) a += toF<T>(fcw[t * Tst + j]) * zs[j];
+    us[t] = a > 0.f ? a : 0.f;
   }
-  for (int t = 0; t < Tst; ++t) {                  // s = sigmoid(W u + b)
+  __syncthreads();
+  if (t < Tst) {                                   // s = sigmoid(W u + b)
     float a = toF<T>(fcb[t]);
-    for (int j = 0; j < Tst; ++j) a += toF<T>(fcw[t * Tst + j]) * u[j];
-    z_out[b * Tst + t] = z[t];
-    u_out[b * Tst + t] = u[t];
+    for (int j = 0; j < Tst; ++j) a += toF<T>(fcw[t * Tst + j]) * us[j];
+    zsum[b * Tst + t] = zs[t];
+    u_out[b * Tst + t] = us[t];
     s_out[b * Tst + t] = stm_sigmoid(a);
   }
 }
 
 // ---- K4 forward part B: out = obs * s[b,t] --------------------------------
-template <typename T>
+// NM (node-major): out is (B,N,T,C), the sequence layout the RNN reads, so no
+// permute copy follows; thread i owns output element i either way.
+template <typename T, bool NM>
 __global__ void gate_scale_kernel(const T* __restrict__ obs,   // (B,T,N,C)
                                   const float* __restrict__ s, // (B,T)
-                                  T* __restrict__ out, int Tst, long NC, long total) {
+                                  T* __restrict__ out, int Tst, int N, int C,
+                                  long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  const long bt = i / NC;
-  out[i] = fromF<T>(toF<T>(obs[i]) * s[bt]);
+  if (!NM) {
+    out[i] = fromF<T>(toF<T>(obs[i]) * s[i / ((long)N * C)]);
+  } else {
+    const int c = i % C;
+    const int t = (i / C) % Tst;
+    const long bn = i / ((long)C * Tst);
+    const long b = bn / N;
+    const int n = bn % N;
+    const long bt = b * Tst + t;
+    out[i] = fromF<T>(toF<T>(obs[(bt * N + n) * C + c]) * s[bt]);
+  }
 }
 
-// ---- K4 backward part A1: ds = sum_{n,c} dout*obs (multi-block + atomics) -
-template <typename T>
+// ---- K4 backward part A: ds reduce + tied-FC backward + dw/db -------------
+// ds[b,t] = sum_{n,c} dout*obs over grid (nchunks, B) with atomics; the last
+// workgroup to arrive for row b (ticket b) runs the FC backward of that row
+// (lanes own columns, as in the forward), leaving dz over ds and the row's
+// dW/db partials; it then arrives at ticket B, and the last row to finish sums
+// the partials over the batch and writes dw / db in fp32 and in the parameter
+// dtype. NM: dout is (B,N,T,C).
+template <typename T, bool NM>
 __global__ void gate_bwd_reduce_kernel(const T* __restrict__ dout, // (B,T,N,C)
                                        const T* __restrict__ obs,  // (B,T,N,C)
                                        float* __restrict__ ds_out, // (B,T) zeroed
+                                       const T* __restrict__ fcw,  // (T,T)
+                                       const float* __restrict__ z,
+                                       const float* __restrict__ u,
+                                       const float* __restrict__ s,
+                                       float* __restrict__ dw_part,   // (B,T,T)
+                                       float* __restrict__ db_part,   // (B,T)
+                                       unsigned* tickets,             // (B+1,) zeroed
+                                       float* __restrict__ dw_f,      // (T,T)
+                                       float* __restrict__ db_f,      // (T,)
+                                       T* __restrict__ dw_out, T* __restrict__ db_out,
                                        int N, int C, int Tst) {
   __shared__ float red[256];
+  // arrival flag: the last word of red (the reduce uses the first 4 *
+  // GATE_MAX_T words, the FC stage the first 2 * GATE_MAX_T)
+  int* last_flag = (int*)&red[255];
   const long b = blockIdx.y;
+  const int B = gridDim.y;
   const long NC = (long)N * C;
   const int nchunks = gridDim.x;
   const long chunk = (NC + nchunks - 1) / nchunks;
@@ -142,9 +183,20 @@ __global__ void gate_bwd_reduce_kernel(const T* __restrict__ dout, // (B,T,N,C)
   for (int t = 0; t < Tst; ++t) dsacc[t] = 0.f;
   const T* db_ = dout + b * Tst * NC;
   const T* ob = obs + b * Tst * NC;
-  for (int t = 0; t < Tst; ++t)
-    for (long i = i0 + threadIdx.x; i < i1; i += blockDim.x)
-      dsacc[t] += toF<T>(db_[t * NC + i]) * toF<T>(ob[t * NC + i]);
+  if (!NM) {
+    for (int t = 0; t < Tst; ++t)
+      for (long i = i0 + threadIdx.x; i < i1; i += blockDim.x)
+        dsacc[t] += toF<T>(db_[t * NC + i]) * toF<T>(ob[t * NC + i]);
+  } else {
+    // same thread -> (i, t) assignment and the same order per (thread, t),
+    // with t innermost: a node's T values of dout share one cache line
+    for (long i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+      const T* dp = db_ + (i / C) * Tst * C + i % C;
+      #pragma unroll
+      for (int t = 0; t < GATE_MAX_T; ++t)
+        if (t < Tst) dsacc[t] += toF<T>(dp[t * C]) * toF<T>(ob[t * NC + i]);
+    }
+  }
   for (int t = 0; t < Tst; ++t) {
     float v = dsacc[t];
     #pragma unroll
@@ -158,50 +210,55 @@ __global__ void gate_bwd_reduce_kernel(const T* __restrict__ dout, // (B,T,N,C)
     }
     __syncthreads();
   }
-}
 
-// ---- K4 backward part A2: tiny per-batch tied-FC backward -----------------
-template <typename T>
-__global__ void gate_bwd_fc_kernel(const float* __restrict__ ds,  // (B,T)
-                                   const T* __restrict__ fcw,     // (T,T)
-                                   const float* __restrict__ z,
-                                   const float* __restrict__ u,
-                                   const float* __restrict__ s,
-                                   float* __restrict__ dz_out,    // (B,T)
-                                   float* __restrict__ dw_part,   // (B,T,T)
-                                   float* __restrict__ db_part,   // (B,T)
-                                   int Tst, int B) {
-  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  // tied double-FC backward: s = sig(W u + b), u = relu(W z + b)
-  float dv2[GATE_MAX_T], du[GATE_MAX_T], dv1[GATE_MAX_T];
-  for (int t = 0; t < Tst; ++t) {
-    const float sv = s[b * Tst + t];
-    dv2[t] = ds[b * Tst + t] * sv * (1.f - sv);
+  if (!stm_last_arriver(&tickets[b], gridDim.x, last_flag)) return;
+  // tied double-FC backward of row b: s = sig(W u + b), u = relu(W z + b)
+  float* dv2 = red;
+  float* dv1 = red + GATE_MAX_T;
+  const int q = threadIdx.x;
+  if (q < Tst) {
+    const float sv = s[b * Tst + q];
+    dv2[q] = ds_out[b * Tst + q] * sv * (1.f - sv);
   }
-  for (int j = 0; j < Tst; ++j) {                   // du = W^T dv2
+  __syncthreads();
+  if (q < Tst) {                                    // du = W^T dv2
     float a = 0.f;
-    for (int t = 0; t < Tst; ++t) a += toF<T>(fcw[t * Tst + j]) * dv2[t];
-    du[j] = a;
+    for (int t = 0; t < Tst; ++t) a += toF<T>(fcw[t * Tst + q]) * dv2[t];
+    dv1[q] = u[b * Tst + q] > 0.f ? a : 0.f;
   }
-  for (int t = 0; t < Tst; ++t) dv1[t] = u[b * Tst + t] > 0.f ? du[t] : 0.f;
-  for (int j = 0; j < Tst; ++j) {                   // dz = W^T dv1
+  __syncthreads();
+  if (q < Tst) {                                    // dz = W^T dv1
     float a = 0.f;
-    for (int t = 0; t < Tst; ++t) a += toF<T>(fcw[t * Tst + j]) * dv1[t];
-    dz_out[b * Tst + j] = a;
+    for (int t = 0; t < Tst; ++t) a += toF<T>(fcw[t * Tst + q]) * dv1[t];
+    ds_out[b * Tst + q] = a;
+    db_part[b * Tst + q] = dv2[q] + dv1[q];
   }
-  // dW partial = dv2 (x) u + dv1 (x) z ; db partial = dv2 + dv1
-  for (int t = 0; t < Tst; ++t) {
-    for (int j = 0; j < Tst; ++j)
-      dw_part[(b * Tst + t) * Tst + j] =
-          dv2[t] * u[b * Tst + j] + dv1[t] * z[b * Tst + j];
-    db_part[b * Tst + t] = dv2[t] + dv1[t];
+  // dW partial = dv2 (x) u + dv1 (x) z
+  if (q < Tst * Tst) {
+    const int t = q / Tst, j = q % Tst;
+    dw_part[(b * Tst + t) * Tst + j] =
+        dv2[t] * u[b * Tst + j] + dv1[t] * z[b * Tst + j];
+  }
+
+  if (!stm_last_arriver(&tickets[B], B, last_flag)) return;
+  if (q < Tst * Tst) {
+    float a = 0.f;
+    for (int bb = 0; bb < B; ++bb) a += dw_part[(long)bb * Tst * Tst + q];
+    dw_f[q] = a;
+    dw_out[q] = fromF<T>(a);
+  }
+  if (q < Tst) {
+    float a = 0.f;
+    for (int bb = 0; bb < B; ++bb) a += db_part[(long)bb * Tst + q];
+    db_f[q] = a;
+    db_out[q] = fromF<T>(a);
   }
 }
 
 // ---- K4 backward part B: dobs = dout*s + dz/N ; dg = dz/N -----------------
-template <typename T>
-__global__ void gate_bwd_scatter_kernel(const T* __restrict__ dout, // (B,T,N,C)
+// NM: dout is (B,N,T,C). dobs == null (obs needs no gradient): only dg.
+template <typename T, bool NM>
+__global__ void gate_bwd_scatter_kernel(const T* __restrict__ dout,
                                         const float* __restrict__ s,
                                         const float* __restrict__ dz, // (B,T)
                                         T* __restrict__ dobs,         // (B,T,N,C)
@@ -214,12 +271,13 @@ __global__ void gate_bwd_scatter_kernel(const T* __restrict__ dout, // (B,T,N,C)
   const long bt = i / NC;
   const long b = bt / Tst;
   const int t = bt % Tst;
+  const int n = (i % NC) / C, c = (i % NC) % C;
   const float dzv = dz[bt] * invN;
-  dobs[i] = fromF<T>(toF<T>(dout[i]) * s[bt] + dzv);
-  if ((i % NC) % C == 0) {
-    const int n = (i % NC) / C;
-    dg[(b * N + n) * (long)Tst + t] = fromF<T>(dzv);
+  if (dobs != nullptr) {
+    const long di = NM ? ((b * N + n) * (long)Tst + t) * C + c : i;
+    dobs[i] = fromF<T>(toF<T>(dout[di]) * s[bt] + dzv);
   }
+  if (c == 0) dg[(b * N + n) * (long)Tst + t] = fromF<T>(dzv);
 }
 
 // ---- K7: head y[b,n] = sum_m feats_m[b,n,:] . w + bias --------------------
@@ -258,12 +316,16 @@ __global__ void head_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ 
 // head wgrad: dw[g] = sum_r dy[r] * fsum[r,g]; db = sum_r dy[r] — a pure
 // bandwidth reduction (replaces the last library GEMM on the step: a
 // hipBLASLt MT64x16x512 tall-skinny at ~85 us for 1x64 output).
-template <typename T>
+// FIN: the last workgroup to arrive (stm_last_arriver, common.h; the ticket
+// sits in the same zeroed workspace as dw / db) writes both in the parameter
+// dtype, so no convert launches follow.
+template <typename T, bool FIN>
 __global__ void head_wgrad_kernel(const T* __restrict__ dy,
                                   const T* __restrict__ fsum,
                                   float* __restrict__ dw,   // (G,) zeroed
                                   float* __restrict__ db,   // (1,) zeroed
-                                  int G, long BN) {
+                                  int G, long BN, unsigned* ticket,
+                                  T* __restrict__ dw_out, T* __restrict__ db_out) {
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const long chunk = (BN + gridDim.x - 1) / gridDim.x;
@@ -299,6 +361,37 @@ __global__ void head_wgrad_kernel(const T* __restrict__ dy,
     if (lane < G) unsafeAtomicAdd(&dw[lane], v);
     if (lane == 0)
       unsafeAtomicAdd(db, redb[0] + redb[1] + redb[2] + redb[3]);
+  }
+  if constexpr (FIN) {
+    // the flag reuses red: wave 0 has consumed it before the helper's barrier
+    if (!stm_last_arriver(ticket, gridDim.x, (int*)&red[0][0])) return;
+    if (threadIdx.x < G) dw_out[threadIdx.x] = fromF<T>(dw[threadIdx.x]);
+    if (threadIdx.x == 64) db_out[0] = fromF<T>(db[0]);
+  }
+}
+
+// dz = dy * (y > 0): the ReLU mask of the graph-conv backward in one pass.
+// The product is formed in fp32 (dy * 1 and dy * 0 are exact), so the result,
+// the sign of a zero included, is what dy * (y > 0).to(dtype) gives.
+template <typename T>
+__global__ void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y,
+                                T* __restrict__ dz, long n, int vec) {
+  const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+  if (i0 >= n) return;
+  auto one = [&](long i) {
+    dz[i] = fromF<T>(toF<T>(dy[i]) * (toF<T>(y[i]) > 0.f ? 1.f : 0.f));
+  };
+  if (vec && i0 + 8 <= n) {   // 16-byte path (vec: all three bases aligned)
+    union { T t[8]; uint4 u; } a, b, o;
+    a.u = *(const uint4*)&dy[i0];
+    b.u = *(const uint4*)&y[i0];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j)
+      o.t[j] = fromF<T>(toF<T>(a.t[j]) * (toF<T>(b.t[j]) > 0.f ? 1.f : 0.f));
+    *(uint4*)&dz[i0] = o.u;
+  } else {   // this thread's own 8 elements (fewer at the end), one by one
+    const long e = i0 + 8 < n ? i0 + 8 : n;
+    for (long i = i0; i < e; ++i) one(i);
   }
 }
 
@@ -379,36 +472,47 @@ static int gate_chunks(int B, long work_per_b) {
 template <typename T>
 static void launch_gate_fwd(hipStream_t st, const T* g, const T* xs,
                             const T* fcw, const T* fcb, const T* obs,
-                            float* z, float* u, float* s, T* out,
-                            int B, int Tst, int N, int C) {
-  // z arrives zeroed and doubles as the zsum atomic target (A2 rescales)
+                            float* z, float* u, float* s, unsigned* tickets,
+                            T* out, int B, int Tst, int N, int C, int nm) {
+  // z and tickets arrive zeroed (one fill); z doubles as the zsum atomic target
   const dim3 gridA(gate_chunks(B, N), B);
   hipLaunchKernelGGL(gate_fwd_reduce_kernel<T>, gridA, dim3(256), 0, st,
-                     g, xs, z, N, Tst);
-  hipLaunchKernelGGL(gate_fwd_fc_kernel<T>, dim3((B + 63) / 64), dim3(64), 0,
-                     st, z, fcw, fcb, z, u, s, N, Tst, B);
-  hipLaunchKernelGGL(gate_scale_kernel<T>, dim3(((long)B * Tst * N * C + 255) / 256),
-                     dim3(256), 0, st, obs, s, out, Tst, (long)N * C,
-                     (long)B * Tst * N * C);
+                     g, xs, z, fcw, fcb, u, s, tickets, N, Tst);
+  const long total = (long)B * Tst * N * C;
+  const dim3 gridB((total + 255) / 256);
+  if (nm)
+    hipLaunchKernelGGL((gate_scale_kernel<T, true>), gridB, dim3(256), 0, st, obs,
+                       s, out, Tst, N, C, total);
+  else
+    hipLaunchKernelGGL((gate_scale_kernel<T, false>), gridB, dim3(256), 0, st, obs,
+                       s, out, Tst, N, C, total);
 }
 
 template <typename T>
 static void launch_gate_bwd(hipStream_t st, const T* dout, const T* obs,
                             const T* fcw, const float* z, const float* u,
                             const float* s, float* dz, float* dw_part,
-                            float* db_part, T* dobs, T* dg,
-                            int B, int Tst, int N, int C) {
+                            float* db_part, unsigned* tickets, float* dw_f,
+                            float* db_f, T* dw, T* db, T* dobs, T* dg,
+                            int B, int Tst, int N, int C, int nm) {
   const long total = (long)B * Tst * N * C;
   const float invN = 1.f / (float)N;
-  // dz arrives zeroed and doubles as the ds atomic target (fc pass rewrites)
+  // dz and tickets arrive zeroed (one fill); dz doubles as the ds atomic target
   const dim3 gridA(gate_chunks(B, (long)N * C), B);
-  hipLaunchKernelGGL(gate_bwd_reduce_kernel<T>, gridA, dim3(256), 0, st,
-                     dout, obs, dz, N, C, Tst);
-  hipLaunchKernelGGL(gate_bwd_fc_kernel<T>, dim3((B + 63) / 64), dim3(64), 0,
-                     st, dz, fcw, z, u, s, dz, dw_part, db_part, Tst, B);
-  hipLaunchKernelGGL(gate_bwd_scatter_kernel<T>, dim3((total + 255) / 256),
-                     dim3(256), 0, st, dout, s, dz, dobs, dg, Tst, N, C, invN,
-                     total);
+  const dim3 gridB((total + 255) / 256);
+  if (nm) {
+    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, true>), gridA, dim3(256), 0, st,
+                       dout, obs, dz, fcw, z, u, s, dw_part, db_part, tickets,
+                       dw_f, db_f, dw, db, N, C, Tst);
+    hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, true>), gridB, dim3(256), 0, st,
+                       dout, s, dz, dobs, dg, Tst, N, C, invN, total);
+  } else {
+    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, false>), gridA, dim3(256), 0, st,
+                       dout, obs, dz, fcw, z, u, s, dw_part, db_part, tickets,
+                       dw_f, db_f, dw, db, N, C, Tst);
+    hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, false>), gridB, dim3(256), 0, st,
+                       dout, s, dz, dobs, dg, Tst, N, C, invN, total);
+  }
 }
 
 }  // namespace
@@ -445,39 +549,45 @@ void stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs,
 }
 
 
+// z (B*T floats) and tickets (B words) share one zero-filled allocation;
+// node_major: out is (B,N,T,C) instead of (B,T,N,C)
 void stmgcn_gate_fwd(void* stream, int dtype, const void* g, const void* xs,
                      const void* fcw, const void* fcb, const void* obs,
-                     float* z, float* u, float* s, void* out,
-                     int B, int Tst, int N, int C) {
+                     float* z, float* u, float* s, unsigned* tickets, void* out,
+                     int B, int Tst, int N, int C, int node_major) {
   hipStream_t st = (hipStream_t)stream;
   switch (dtype) {
     case STM_F32:
-      launch_gate_fwd<float>(st, (const float*)g, (const float*)xs, (const float*)fcw, (const float*)fcb, (const float*)obs, z, u, s, (float*)out, B, Tst, N, C);
+      launch_gate_fwd<float>(st, (const float*)g, (const float*)xs, (const float*)fcw, (const float*)fcb, (const float*)obs, z, u, s, tickets, (float*)out, B, Tst, N, C, node_major);
       break;
     case STM_BF16:
-      launch_gate_fwd<__hip_bfloat16>(st, (const __hip_bfloat16*)g, (const __hip_bfloat16*)xs, (const __hip_bfloat16*)fcw, (const __hip_bfloat16*)fcb, (const __hip_bfloat16*)obs, z, u, s, (__hip_bfloat16*)out, B, Tst, N, C);
+      launch_gate_fwd<__hip_bfloat16>(st, (const __hip_bfloat16*)g, (const __hip_bfloat16*)xs, (const __hip_bfloat16*)fcw, (const __hip_bfloat16*)fcb, (const __hip_bfloat16*)obs, z, u, s, tickets, (__hip_bfloat16*)out, B, Tst, N, C, node_major);
       break;
     case STM_F16:
-      launch_gate_fwd<__half>(st, (const __half*)g, (const __half*)xs, (const __half*)fcw, (const __half*)fcb, (const __half*)obs, z, u, s, (__half*)out, B, Tst, N, C);
+      launch_gate_fwd<__half>(st, (const __half*)g, (const __half*)xs, (const __half*)fcw, (const __half*)fcb, (const __half*)obs, z, u, s, tickets, (__half*)out, B, Tst, N, C, node_major);
       break;
   }
 }
 
-
+// dz (B*T floats) and tickets (B + 1 words) share one zero-filled allocation;
+// dw_f/db_f: fp32 sums over the batch, dw/db the same in `dtype`; dobs may be
+// null (obs needs no gradient); node_major: dout is (B,N,T,C)
 void stmgcn_gate_bwd(void* stream, int dtype, const void* dout, const void* obs,
                      const void* fcw, const float* z, const float* u,
                      const float* s, float* dz, float* dw_part, float* db_part,
-                     void* dobs, void* dg, int B, int Tst, int N, int C) {
+                     unsigned* tickets, float* dw_f, float* db_f, void* dw,
+                     void* db, void* dobs, void* dg, int B, int Tst, int N, int C,
+                     int node_major) {
   hipStream_t st = (hipStream_t)stream;
   switch (dtype) {
     case STM_F32:
-      launch_gate_bwd<float>(st, (const float*)dout, (const float*)obs, (const float*)fcw, z, u, s, dz, dw_part, db_part, (float*)dobs, (float*)dg, B, Tst, N, C);
+      launch_gate_bwd<float>(st, (const float*)dout, (const float*)obs, (const float*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (float*)dw, (float*)db, (float*)dobs, (float*)dg, B, Tst, N, C, node_major);
       break;
     case STM_BF16:
-      launch_gate_bwd<__hip_bfloat16>(st, (const __hip_bfloat16*)dout, (const __hip_bfloat16*)obs, (const __hip_bfloat16*)fcw, z, u, s, dz, dw_part, db_part, (__hip_bfloat16*)dobs, (__hip_bfloat16*)dg, B, Tst, N, C);
+      launch_gate_bwd<__hip_bfloat16>(st, (const __hip_bfloat16*)dout, (const __hip_bfloat16*)obs, (const __hip_bfloat16*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (__hip_bfloat16*)dw, (__hip_bfloat16*)db, (__hip_bfloat16*)dobs, (__hip_bfloat16*)dg, B, Tst, N, C, node_major);
       break;
     case STM_F16:
-      launch_gate_bwd<__half>(st, (const __half*)dout, (const __half*)obs, (const __half*)fcw, z, u, s, dz, dw_part, db_part, (__half*)dobs, (__half*)dg, B, Tst, N, C);
+      launch_gate_bwd<__half>(st, (const __half*)dout, (const __half*)obs, (const __half*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (__half*)dw, (__half*)db, (__half*)dobs, (__half*)dg, B, Tst, N, C, node_major);
       break;
   }
 }
@@ -512,9 +622,37 @@ void stmgcn_head_wgrad(void* stream, int dtype, const void* dy,
   if (nblk < 1) nblk = 1;
   dim3 grid((unsigned)nblk);
   switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(head_wgrad_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)fsum, dw, db, G, BN); break;
-    case STM_BF16: hipLaunchKernelGGL(head_wgrad_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)fsum, dw, db, G, BN); break;
-    case STM_F16: hipLaunchKernelGGL(head_wgrad_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)fsum, dw, db, G, BN); break;
+    case STM_F32: hipLaunchKernelGGL((head_wgrad_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
+    case STM_BF16: hipLaunchKernelGGL((head_wgrad_kernel<__hip_bfloat16, false>), grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
+    case STM_F16: hipLaunchKernelGGL((head_wgrad_kernel<__half, false>), grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
+  }
+}
+
+// finishing form: dw_out (G,) / db_out (1,) in the dtype of dy
+void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy,
+                             const void* fsum, float* dw, float* db,
+                             unsigned* ticket, void* dw_out, void* db_out,
+                             int G, long BN) {
+  long nblk = (BN + 255) / 256;
+  if (nblk > 512) nblk = 512;
+  if (nblk < 1) nblk = 1;
+  dim3 grid((unsigned)nblk);
+  switch (dtype) {
+    case STM_F32: hipLaunchKernelGGL((head_wgrad_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)fsum, dw, db, G, BN, ticket, (float*)dw_out, (float*)db_out); break;
+    case STM_BF16: hipLaunchKernelGGL((head_wgrad_kernel<__hip_bfloat16, true>), grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)fsum, dw, db, G, BN, ticket, (__hip_bfloat16*)dw_out, (__hip_bfloat16*)db_out); break;
+    case STM_F16: hipLaunchKernelGGL((head_wgrad_kernel<__half, true>), grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)fsum, dw, db, G, BN, ticket, (__half*)dw_out, (__half*)db_out); break;
+  }
+}
+
+void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,
+                     void* dz, long n) {
+  if (n <= 0) return;
+  const int vec = (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dz) & 15) == 0;
+  dim3 grid((unsigned)((n + 2047) / 2048));
+  switch (dtype) {
+    case STM_BF16: hipLaunchKernelGGL(relu_bwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)y, (__hip_bfloat16*)dz, n, vec); break;
+    case STM_F16: hipLaunchKernelGGL(relu_bwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)y, (__half*)dz, n, vec); break;
+    default: printf("stmgcn_relu_bwd: unsupported dtype %d (bf16/f16 only)\n", dtype);
   }
 }
 

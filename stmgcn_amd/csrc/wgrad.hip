@@ -126,13 +126,34 @@ __device__ __forceinline__ typename WFrag8<T>::type frag_from(
 // (STMGCN_WGRAD_SPLIT_L0=1). layer = blockIdx.y + lbase. Chunks are whole
 // tiles (tpc per workgroup); an odd tile count leaves the second half of the
 // last K-step zero.
-template <typename T, bool L0CIN1, int GT>
+//
+// FIN (the finishing form): after its atomics every workgroup arrives at its
+// layer's ticket (stm_last_arriver, common.h); the last one of a layer reads
+// that layer's 129 KiB of fp32 sums back and writes dw_ih, dw_hh, db_ih,
+// db_hh in the parameter dtype and in their final shapes into `fin.out`
+// (layout: lstm_grads_layer_off). One ticket per layer, so up to L last
+// arrivers share the conversion. GRU rows are un-packed on the way
+// (q-slots [r|z|n_in|n_hid]: dw_ih/db_ih = rows [:3H], dw_hh/db_hh = rows
+// [:2H] + [3H:]); LSTM writes the one bias sum to both db_ih and db_hh.
+template <typename T>
+struct LstmFin {
+  unsigned* tickets;   // (L,) zero at launch, same fill as the accumulators
+  T* out;              // flat parameter-dtype gradient buffer
+  int gru, cin;
+};
+
+// element offset of layer l's [dw_ih | dw_hh | db_ih | db_hh] block
+__host__ __device__ inline long lstm_grads_layer_off(int l, int GH, int cin) {
+  return l == 0 ? 0 : (long)GH * (cin + 64 + 2) + (long)(l - 1) * GH * (64 + 64 + 2);
+}
+
+template <typename T, bool L0CIN1, int GT, bool FIN>
 __global__ void __launch_bounds__(GT * 2, 1)
 lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
                   const T* __restrict__ x, float* __restrict__ dwih,
                   float* __restrict__ dwhh, float* __restrict__ db,
                   long R, long S_pad, int S, int Tst, int L, int lbase,
-                  int cin1, long tpc) {
+                  int cin1, long tpc, LstmFin<T> fin) {
   using frag = typename WFrag8<T>::type;
   constexpr int NTHR = GT * 2;      // one wave per 32 gate rows
   constexpr int MTG = 2;            // gate m-tiles per wave
@@ -150,7 +171,10 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   const long tb0 = (long)blockIdx.x * tpc;
   const long tb1 = (tb0 + tpc < ntile) ? tb0 + tpc : ntile;
   const long tp0 = S_pad / SEQ_TILE;          // tiles of t == 0 (no h_{t-1})
-  if (tb0 >= tb1) return;
+  // An empty chunk (the host's chunking leaves none) has nothing to add; in
+  // the finishing form it still has to arrive, or its layer would never be
+  // finished: it falls through with every load guarded off and adds zeros.
+  if (!FIN && tb0 >= tb1) return;
 
   const T* dA_l = dA + (long)layer * R * STM_DA_GATES;
   const T* hp_l = hseq + (long)layer * R * 64;       // index r - S_pad
@@ -308,12 +332,71 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
     v += __shfl_xor(v, 32, 64);
     if (lgrp == 0) unsafeAtomicAdd(&db[layer * 256 + gw + mt * 16 + l16], v);
   }
+
+  if constexpr (FIN) {
+    if (!stm_last_arriver(&fin.tickets[layer], gridDim.x * gridDim.z, (int*)lds))
+      return;
+    // packed gate row m -> output row (or -1: a zero GRU slot)
+    const int GH = fin.gru ? 192 : 256;
+    const int cin_l = l0 ? fin.cin : 64;
+    auto row_ih = [&](int m) { return m < GH ? m : -1; };
+    auto row_hh = [&](int m) {
+      return !fin.gru ? m : (m < 128 ? m : (m >= 192 ? m - 64 : -1));
+    };
+    T* o_ih = fin.out + lstm_grads_layer_off(layer, GH, fin.cin);
+    T* o_hh = o_ih + (long)GH * cin_l;
+    T* o_bi = o_hh + (long)GH * 64;
+    T* o_bh = o_bi + GH;
+    const float* dbl = db + layer * 256;
+    // Every load is issued before the first store (the outputs may alias the
+    // sums as far as the compiler knows, so a load-store-load loop would pay
+    // one memory round trip per iteration on this serial tail): float4 i of a
+    // (256, 64) matrix is row i >> 4, columns 4 * (i & 15).
+    constexpr int IT = 256 * 16 / NTHR;   // float4 per thread per matrix
+    constexpr int BT = 256 / NTHR ? 256 / NTHR : 1;
+    const bool dense = cin_l == 64;
+    float4 vh[IT], vi[IT];
+    float vb[BT], vc[BT];
+    #pragma unroll
+    for (int k = 0; k < IT; ++k) {
+      const int i = threadIdx.x + k * NTHR;
+      vh[k] = *(const float4*)&whh[i * 4];
+      vi[k] = dense ? *(const float4*)&wih[i * 4] : float4{0.f, 0.f, 0.f, 0.f};
+    }
+    #pragma unroll
+    for (int k = 0; k < BT; ++k) {
+      const int m = threadIdx.x + k * NTHR;
+      vb[k] = m < 256 ? dbl[m] : 0.f;
+      vc[k] = (!dense && m < 256) ? wih[m * 64] : 0.f;
+    }
+    #pragma unroll
+    for (int k = 0; k < IT; ++k) {
+      const int i = threadIdx.x + k * NTHR;
+      const int m = i >> 4, n4 = (i & 15) * 4;
+      const int rh = row_hh(m), ri = row_ih(m);
+      if (rh >= 0)
+        stm_store4<T>(&o_hh[rh * 64 + n4], vh[k].x, vh[k].y, vh[k].z, vh[k].w);
+      if (dense && ri >= 0)
+        stm_store4<T>(&o_ih[ri * 64 + n4], vi[k].x, vi[k].y, vi[k].z, vi[k].w);
+    }
+    #pragma unroll
+    for (int k = 0; k < BT; ++k) {
+      const int m = threadIdx.x + k * NTHR;
+      if (m >= 256) continue;
+      const int ri = row_ih(m), rh = row_hh(m);
+      if (ri >= 0) o_bi[ri] = fromF<T>(vb[k]);
+      if (rh >= 0) o_bh[rh] = fromF<T>(vb[k]);
+      if (!dense && ri >= 0) o_ih[ri] = fromF<T>(vc[k]);
+    }
+  }
 }
 
-extern "C" void stmgcn_lstm_wgrad(void* stream_v, int dtype, const void* dA,
-                                  const void* hseq, const void* x, float* dwih,
-                                  float* dwhh, float* db, long R, long S_pad,
-                                  int S, int Tst, int L, int cin) {
+// tickets/out == null: the accumulate-only form (fp32 sums left in place)
+static void lstm_wgrad_launch(void* stream_v, int dtype, const void* dA,
+                              const void* hseq, const void* x, float* dwih,
+                              float* dwhh, float* db, long R, long S_pad,
+                              int S, int Tst, int L, int cin,
+                              unsigned* tickets, void* out, int gru) {
   static long env_chunks = -1;   // STMGCN_WGRAD_CHUNKS: perf experiments
   static int env_gt = -1;        // STMGCN_WGRAD_GT=128: gate-split variant
   static int env_split = 0;      // STMGCN_WGRAD_SPLIT_L0=1: own launch for
@@ -340,35 +423,59 @@ extern "C" void stmgcn_lstm_wgrad(void* stream_v, int dtype, const void* dA,
   nchunks = (ntile + tpc - 1) / tpc;
   const size_t lds = 2 * 2 * 8192;   // double-buffered hpT | hxT, 64-row steps
   hipStream_t stream = (hipStream_t)stream_v;
-  auto launch = [&](auto tptr, auto gtc) {
+  auto launch = [&](auto tptr, auto gtc, auto finc) {
     using TT = std::remove_pointer_t<decltype(tptr)>;
     constexpr int GT = decltype(gtc)::value;   // gate rows per workgroup
+    constexpr bool FIN = decltype(finc)::value;
     const dim3 blk(GT * 2);
+    const LstmFin<TT> fin{tickets, (TT*)out, gru, cin};
     if (cin == 1 && env_split) {
       // layer 0 (single ih column) and layers >= 1 as separate instantiations
-      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, true, GT>),
+      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, true, GT, FIN>),
                          dim3((unsigned)nchunks, 1, 256 / GT), blk, lds, stream,
                          (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, 1, tpc);
+                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, 1, tpc, fin);
       if (L > 1)
-        hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT>),
+        hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT, FIN>),
                            dim3((unsigned)nchunks, L - 1, 256 / GT), blk, lds,
                            stream, (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                           dwih, dwhh, db, R, S_pad, S, Tst, L, 1, 0, tpc);
+                           dwih, dwhh, db, R, S_pad, S, Tst, L, 1, 0, tpc, fin);
     } else {
-      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT>),
+      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT, FIN>),
                          dim3((unsigned)nchunks, L, 256 / GT), blk, lds, stream,
                          (const TT*)dA, (const TT*)hseq, (const TT*)x,
                          dwih, dwhh, db, R, S_pad, S, Tst, L, 0, cin == 1 ? 1 : 0,
-                         tpc);
+                         tpc, fin);
     }
   };
-  auto by_gt = [&](auto tptr) {
-    if (env_gt == 128) launch(tptr, std::integral_constant<int, 128>{});
-    else launch(tptr, std::integral_constant<int, 256>{});
+  auto by_gt = [&](auto tptr, auto finc) {
+    if (env_gt == 128) launch(tptr, std::integral_constant<int, 128>{}, finc);
+    else launch(tptr, std::integral_constant<int, 256>{}, finc);
   };
-  if (dtype == STM_BF16) by_gt((__hip_bfloat16*)nullptr);
-  else if (dtype == STM_F16) by_gt((__half*)nullptr);
+  auto by_fin = [&](auto tptr) {
+    if (out != nullptr) by_gt(tptr, std::true_type{});
+    else by_gt(tptr, std::false_type{});
+  };
+  if (dtype == STM_BF16) by_fin((__hip_bfloat16*)nullptr);
+  else if (dtype == STM_F16) by_fin((__half*)nullptr);
+}
+
+extern "C" void stmgcn_lstm_wgrad(void* stream, int dtype, const void* dA,
+                                  const void* hseq, const void* x, float* dwih,
+                                  float* dwhh, float* db, long R, long S_pad,
+                                  int S, int Tst, int L, int cin) {
+  lstm_wgrad_launch(stream, dtype, dA, hseq, x, dwih, dwhh, db, R, S_pad, S,
+                    Tst, L, cin, nullptr, nullptr, 0);
+}
+
+extern "C" void stmgcn_lstm_wgrad_grads(void* stream, int dtype, const void* dA,
+                                        const void* hseq, const void* x,
+                                        float* dwih, float* dwhh, float* db,
+                                        unsigned* tickets, void* out, long R,
+                                        long S_pad, int S, int Tst, int L,
+                                        int cin, int gru) {
+  lstm_wgrad_launch(stream, dtype, dA, hseq, x, dwih, dwhh, db, R, S_pad, S,
+                    Tst, L, cin, tickets, out, gru);
 }
 
 // ===========================================================================
@@ -383,13 +490,26 @@ extern "C" void stmgcn_lstm_wgrad(void* stream_v, int dtype, const void* dA,
 // ALL supports' dW_k land in one launch with dZ streamed ONCE (the
 // (B,N,K_s,C) concat stack never exists). CA must be a multiple of 8 so
 // every 8-col fragment stays within one source.
+//
+// FIN (the finishing form): the workgroup that draws the launch's last ticket
+// (stm_last_arriver, common.h) reads the <= 64 KiB of fp32 sums back and
+// writes dW (M, N) and db (N,) in the parameter dtype. C, db and the ticket
+// share one zero-filled fp32 workspace; two launches that share a workspace
+// (the dual gconv's forward and backward source groups) take one ticket each
+// and finish their own rows.
 struct AtbSrc { const void* a[4]; };
 
 template <typename T>
+struct AtbFin {
+  unsigned* ticket;   // zero at launch
+  T *dW, *dbo;        // (M, N) and (N,) outputs; dbo null when db is
+};
+
+template <typename T, bool FIN>
 __global__ void __launch_bounds__(256, 1)
 atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
                  float* __restrict__ C, float* __restrict__ db,
-                 long rows, int M, int N) {
+                 long rows, int M, int N, AtbFin<T> fin) {
   using frag = typename WFrag8<T>::type;
   extern __shared__ char lds[];
   char* AT = lds;                  // [256][32] -> 16 KiB
@@ -514,12 +634,33 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
       unsafeAtomicAdd(&db[n], v);
     }
   }
+
+  if constexpr (FIN) {
+    if (!stm_last_arriver(fin.ticket, gridDim.x, (int*)lds)) return;
+    const int n4s = M * N / 4;   // N is a multiple of 8
+    // four loads in flight per thread before their stores (see lstm_wgrad)
+    for (int i0 = threadIdx.x; i0 < n4s; i0 += 4 * 256) {
+      float4 v[4];
+      #pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * 256;
+        v[k] = i < n4s ? *(const float4*)&C[i * 4] : float4{0.f, 0.f, 0.f, 0.f};
+      }
+      #pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + k * 256;
+        if (i < n4s) stm_store4<T>(&fin.dW[i * 4], v[k].x, v[k].y, v[k].z, v[k].w);
+      }
+    }
+    if (db && threadIdx.x < N) fin.dbo[threadIdx.x] = fromF<T>(db[threadIdx.x]);
+  }
 }
 
-extern "C" void stmgcn_atb_wgrad_multi(void* stream_v, int dtype,
-                                       const void** As, int nsrc, int CA,
-                                       const void* B, float* C, float* db,
-                                       long rows, int N) {
+// fin_ticket == null: the accumulate-into form (fp32 sums left in C / db)
+static void atb_wgrad_launch(void* stream_v, int dtype, const void** As,
+                             int nsrc, int CA, const void* B, float* C,
+                             float* db, long rows, int N, unsigned* fin_ticket,
+                             void* fin_dW, void* fin_db) {
   // fill the 256-CU chip: ~128 rows per workgroup minimum (4 K-tiles)
   long nchunks = (rows + 127) / 128;
   if (nchunks > 512) nchunks = 512;
@@ -530,15 +671,37 @@ extern "C" void stmgcn_atb_wgrad_multi(void* stream_v, int dtype,
   AtbSrc src{};
   for (int i = 0; i < nsrc && i < 4; ++i) src.a[i] = As[i];
   hipStream_t stream = (hipStream_t)stream_v;
-  if (dtype == STM_BF16)
-    hipLaunchKernelGGL((atb_wgrad_kernel<__hip_bfloat16>), grid, blk, lds,
-                       stream, src, CA, (const __hip_bfloat16*)B, C, db, rows,
-                       M, N);
-  else if (dtype == STM_F16)
-    hipLaunchKernelGGL((atb_wgrad_kernel<__half>), grid, blk, lds, stream,
-                       src, CA, (const __half*)B, C, db, rows, M, N);
+  auto launch = [&](auto tptr, auto finc) {
+    using TT = std::remove_pointer_t<decltype(tptr)>;
+    constexpr bool FIN = decltype(finc)::value;
+    const AtbFin<TT> fin{fin_ticket, (TT*)fin_dW, (TT*)fin_db};
+    hipLaunchKernelGGL((atb_wgrad_kernel<TT, FIN>), grid, blk, lds, stream, src,
+                       CA, (const TT*)B, C, db, rows, M, N, fin);
+  };
+  auto by_fin = [&](auto tptr) {
+    if (fin_ticket != nullptr) launch(tptr, std::true_type{});
+    else launch(tptr, std::false_type{});
+  };
+  if (dtype == STM_BF16) by_fin((__hip_bfloat16*)nullptr);
+  else if (dtype == STM_F16) by_fin((__half*)nullptr);
   else
     printf("stmgcn_atb_wgrad: unsupported dtype %d (bf16/f16 only)\n", dtype);
+}
+
+extern "C" void stmgcn_atb_wgrad_multi(void* stream, int dtype, const void** As,
+                                       int nsrc, int CA, const void* B, float* C,
+                                       float* db, long rows, int N) {
+  atb_wgrad_launch(stream, dtype, As, nsrc, CA, B, C, db, rows, N, nullptr,
+                   nullptr, nullptr);
+}
+
+extern "C" void stmgcn_atb_wgrad_multi_grads(void* stream, int dtype,
+                                             const void** As, int nsrc, int CA,
+                                             const void* B, float* C, float* db,
+                                             unsigned* ticket, void* dW,
+                                             void* dbo, long rows, int N) {
+  atb_wgrad_launch(stream, dtype, As, nsrc, CA, B, C, db, rows, N, ticket, dW,
+                   dbo);
 }
 
 extern "C" void stmgcn_atb_wgrad(void* stream_v, int dtype, const void* A,

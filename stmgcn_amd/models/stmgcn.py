@@ -133,8 +133,11 @@ class CGRNNCellParams(nn.Module):
                     getattr(self, f"bias_ih_l{l}"), getattr(self, f"bias_hh_l{l}")]
         return out
 
-    def forward(self, x: torch.Tensor, h0: torch.Tensor, c0: Optional[torch.Tensor],
+    def forward(self, x: torch.Tensor, h0: Optional[torch.Tensor] = None,
+                c0: Optional[torch.Tensor] = None,
                 return_sequences: bool = False) -> torch.Tensor:
+        """h0 None: zero initial states, built by ops.rnn_forward only on the
+        paths that read them (CPU oracle, stock-torch floor)."""
         return ops.rnn_forward(self.cell, x, self.flat_weights(), h0, c0,
                                return_sequences)
 
@@ -167,11 +170,13 @@ class CG_LSTM(nn.Module):
         B, T, N, C = obs_seq.shape
         x_seq = ops.seqsum_permute(obs_seq)                   # (B,N,T), K3
         g = self.gconv_temporal_feats(adj, x_seq)             # (B,N,T), K1+K2
-        gated = ops.contextual_gate(obs_seq, g, self.fc.weight, self.fc.bias)  # K4
-        flat = gated.permute(0, 2, 1, 3).reshape(B * N, T, C)  # node-major seqs
-        h0 = obs_seq.new_zeros(self.num_layers, B * N, self.hidden_dim)
-        c0 = h0.clone() if self.cell == "lstm" else None
-        out = self.lstm(flat, h0, c0, return_sequences)       # K5/K6
+        # K4, written node-major (B,N,T,C) — the RNN's sequence layout — from
+        # the x_seq already at hand; zero initial states (reference
+        # STMGCN.py:93-98) are implied, not materialized, on the HIP path
+        gated = ops.contextual_gate(obs_seq, g, self.fc.weight, self.fc.bias,
+                                    xs=x_seq, node_major=True)
+        flat = gated.reshape(B * N, T, C)
+        out = self.lstm(flat, None, None, return_sequences)   # K5/K6
         if return_sequences:
             return out.reshape(B, N, T, self.hidden_dim).permute(0, 2, 1, 3)
         return out.reshape(B, N, self.hidden_dim)

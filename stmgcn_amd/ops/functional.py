@@ -73,22 +73,38 @@ def gconv_mix(A, x: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor],
 
 
 def contextual_gate(obs_seq: torch.Tensor, gconv_out: torch.Tensor,
-                    fc_weight: torch.Tensor, fc_bias: torch.Tensor) -> torch.Tensor:
-    """Contextual gating (eqs.6-9, weight-tied FC — reference STMGCN.py:36-44)."""
+                    fc_weight: torch.Tensor, fc_bias: torch.Tensor,
+                    xs: Optional[torch.Tensor] = None,
+                    node_major: bool = False) -> torch.Tensor:
+    """Contextual gating (eqs.6-9, weight-tied FC — reference STMGCN.py:36-44).
+
+    xs: the caller's seqsum_permute(obs_seq), if it has one (the HIP path then
+    skips recomputing it). node_major: return (B, N, T, C) — the layout the RNN
+    consumes — instead of (B, T, N, C); the HIP path writes it directly, the
+    others return the permuted view."""
     if obs_seq.is_cuda and impl_mode() == "hip":
         from .hip_ops import contextual_gate_hip
-        return contextual_gate_hip(obs_seq, gconv_out, fc_weight, fc_bias)
-    return ref.contextual_gate(obs_seq, gconv_out, fc_weight, fc_bias)
+        return contextual_gate_hip(obs_seq, gconv_out, fc_weight, fc_bias, xs,
+                                   node_major)
+    out = ref.contextual_gate(obs_seq, gconv_out, fc_weight, fc_bias)
+    return out.permute(0, 2, 1, 3) if node_major else out
 
 
 def rnn_forward(cell: str, x: torch.Tensor, weights: List[torch.Tensor],
-                h0: torch.Tensor, c0: Optional[torch.Tensor],
+                h0: Optional[torch.Tensor], c0: Optional[torch.Tensor],
                 return_sequences: bool = False) -> torch.Tensor:
     """Multi-layer LSTM/GRU over (B*N, T, C) — the dominant-FLOP op
-    (reference STMGCN.py:47-50). GPU: persistent fused HIP kernel."""
+    (reference STMGCN.py:47-50). GPU: persistent fused HIP kernel.
+
+    h0 None means zero initial states (what the model always uses): the fused
+    kernels start from zero without reading a tensor, so the zeros are built
+    only on the paths that read them."""
     if x.is_cuda and impl_mode() == "hip":
         from .hip_ops import FusedRNNFn
         return FusedRNNFn.apply(cell, x, h0, c0, return_sequences, *weights)
+    if h0 is None:
+        h0 = x.new_zeros(len(weights) // 4, x.shape[0], weights[1].shape[1])
+        c0 = h0.clone() if cell == "lstm" else None
     if x.is_cuda:  # stock-torch floor mode: the reference's nn.LSTM backend
         from .hip_ops import _vf_rnn
         return _vf_rnn(cell, x, h0, c0, return_sequences, list(weights))

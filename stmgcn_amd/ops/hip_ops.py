@@ -11,6 +11,11 @@ Kernel coverage (all landed; SURVEY §2.4 op numbers in parentheses):
     (wgrad.hip). GRU rides the 4-slot packing documented on FusedLSTMFn.
   - SeqsumPermuteFn (K3), GateFn (K4), HeadFn (K7), FusedMSELossFn (K8);
     the K9 Adam kernel is driven by train/fused_adam.py.
+The reduction kernels (wgrad, head wgrad, the gate's reduces) finish their own
+outputs — the last workgroup to arrive rounds the fp32 sums to the parameter
+dtype and writes the gradients in their final shapes — so the backward
+methods below add no convert / fill / slice launches of their own when the
+parameters have the activations' dtype.
 Numerics tests compare every Function against the fp32 oracle in
 reference_impl.py (tests/test_gpu_kernels.py).
 """
@@ -148,36 +153,48 @@ class ChebGconvFn(torch.autograd.Function):
         if ctx.fused:
             x, Wd, W, y = ctx.saved_tensors[:4]
             ps = ctx.saved_tensors[4:]       # recurrence states from forward
-            if ctx.act == "relu":
-                dz = (dy * (y > 0).to(dy.dtype)).contiguous()
-            else:
+            # parameters in the activations' dtype (the training setup): the
+            # mask is one kernel and the wgrad kernel rounds dW / db itself
+            fast = W.dtype == dy.dtype
+            if ctx.act != "relu":
                 dz = dy.contiguous()
+            elif fast:
+                dz = C.relu_bwd(dy, y)
+            else:
+                dz = (dy * (y > 0).to(dy.dtype)).contiguous()
             dual, single = csr.kind == "dual", csr.kind == "single"
             K_s = csr.K_supports
             Cin, Cout = ctx.cin, dz.shape[-1]
-            if dual:
+            if not ctx.needs_input_grad[0]:
+                # x came from the input data (the temporal gconv in training)
+                dX = None
+            elif dual:
                 gb = csr.dual
-                K = gb.K_supports - 1
                 dX = C.dual_gconv_fused_bwd_dx(
                     dz, Wd, csr.row_ptr_t, csr.col_idx_t, csr.vals_t,
-                    gb.row_ptr_t, gb.col_idx_t, gb.vals_t, K)
+                    gb.row_ptr_t, gb.col_idx_t, gb.vals_t, gb.K_supports - 1)
             else:
                 dX = C.cheb_gconv_fused_bwd_dx(dz, Wd, csr.row_ptr_t,
                                                csr.col_idx_t, csr.vals_t, K_s,
                                                single)
             # ---- dW/db: multi-source MFMA reductions over the saved
             # recurrence states (no concat stack), <= 4 sources per launch
+            dz2 = dz.reshape(-1, Cout)
+            srcs = [p.reshape(-1, Cin)
+                    for p in (ps if single else (x,) + tuple(ps))]
+            # dual: rows [0,(K+1)Cin): x, pf_1..pf_K (+ db); rest: pb_1..pb_K
+            split = csr.dual.K_supports if dual else len(srcs)
+            if fast:
+                outs = C.atb_wgrad_multi_grads(srcs, dz2, split, ctx.has_b)
+                return (dX, outs[0], outs[1] if ctx.has_b else None,
+                        None, None, None)
             dWf = torch.zeros(K_s * Cin, Cout, dtype=torch.float32,
                               device=dz.device)
             db_f = (torch.zeros(Cout, dtype=torch.float32, device=dz.device)
                     if ctx.has_b else None)
-            dz2 = dz.reshape(-1, Cout)
-            srcs = [p.reshape(-1, Cin)
-                    for p in (ps if single else (x,) + tuple(ps))]
             if dual:
-                # rows [0,(K+1)Cin): x, pf_1..pf_K (+ db); rest: pb_1..pb_K
-                C.atb_wgrad_multi(srcs[:K + 1], dz2, dWf[:(K + 1) * Cin], db_f)
-                C.atb_wgrad_multi(srcs[K + 1:], dz2, dWf[(K + 1) * Cin:], None)
+                C.atb_wgrad_multi(srcs[:split], dz2, dWf[:split * Cin], db_f)
+                C.atb_wgrad_multi(srcs[split:], dz2, dWf[split * Cin:], None)
             else:
                 C.atb_wgrad_multi(srcs, dz2, dWf, db_f)   # dz streamed once
             return (dX, dWf.to(W.dtype),
@@ -220,11 +237,14 @@ class ChebGconvFn(torch.autograd.Function):
         return dX, dW, db, None, None, None
 
 
-def contextual_gate_hip(obs_seq, gconv_out, fc_weight, fc_bias):
+def contextual_gate_hip(obs_seq, gconv_out, fc_weight, fc_bias, xs=None,
+                        node_major=False):
     if obs_seq.shape[1] <= 16:
-        return GateFn.apply(obs_seq, gconv_out, fc_weight, fc_bias)
+        return GateFn.apply(obs_seq, gconv_out, fc_weight, fc_bias, xs,
+                            node_major)
     _fallback(f"contextual gate with T={obs_seq.shape[1]} > 16")
-    return ref.contextual_gate(obs_seq, gconv_out, fc_weight, fc_bias)
+    out = ref.contextual_gate(obs_seq, gconv_out, fc_weight, fc_bias)
+    return out.permute(0, 2, 1, 3) if node_major else out
 
 
 def _vf_rnn(cell, x, h0, c0, return_sequences, weights):
@@ -304,15 +324,27 @@ class FusedLSTMFn(torch.autograd.Function):
         x, cseq, gates, hseq = ctx.saved_tensors[:4]
         w_ih = ctx.saved_tensors[4:4 + L]        # packed for GRU
         w_hh = ctx.saved_tensors[4 + L:4 + 2 * L]
-        w_ihT = [w.t().contiguous() for w in w_ih]
-        w_hhT = [w.t().contiguous() for w in w_hh]
         x = x.contiguous()
+        # parameters in the activations' dtype (the training setup): one pack
+        # launch for every transposed weight, and lstm_wgrad rounds, slices
+        # and un-packs its own outputs — backward is pack, lstm_bwd, one fill
+        # + lstm_wgrad, nothing else
+        fast = all(w.dtype == x.dtype for w in ctx.saved_tensors[4:])
+        if fast:
+            wT = C.lstm_pack_bwd_weights(list(w_ih), list(w_hh))
+            w_ihT, w_hhT = wT[:L], wT[L:]
+        else:
+            w_ihT = [w.t().contiguous() for w in w_ih]
+            w_hhT = [w.t().contiguous() for w in w_hh]
         dx, dA = C.lstm_bwd(dout, x, cseq, gates, w_ihT, w_hhT, ctx.ret_seq,
                             ctx.gru)
         S, Tst, cin = x.shape
         # ---- weight grads: ONE batched reduction-GEMM launch for all layers
         # (wgrad.hip; replaces 5 hipBLASLt GEMMs + 3 cat + 3 colsum per call
         # that measured 47.8% of step time — profiles/r01_*)
+        if fast:
+            return (dx, None, None, None,
+                    *C.lstm_wgrad_grads(dA, hseq, x, ctx.gru))
         dwih, dwhh, dbf = C.lstm_wgrad(dA, hseq, x)
         grads = []
         H = 64
@@ -352,6 +384,9 @@ class FusedRNNFn:
             f"fused {cell} with dtype={x.dtype}, C_in={x.shape[-1]}, "
             f"T={x.shape[1]}, hidden={tuple(weights[1].shape)} "
             "(served: bf16/f16, C_in in {1,64}, T<=16, H=64)")
+        if h0 is None:   # the fused kernels start from zero and never read them
+            h0 = x.new_zeros(len(weights) // 4, x.shape[0], weights[1].shape[1])
+            c0 = torch.zeros_like(h0) if cell == "lstm" else None
         return _vf_rnn(cell, x, h0, c0, return_sequences, weights)
 
 
@@ -385,27 +420,39 @@ class GateFn(torch.autograd.Function):
     """K4: fused contextual gate. The kernel folds the gradient of the
     residual x_seq path (x_seq = sum_c obs) directly into dobs, so the xs
     input gets no separate grad here; the gconv path (xs -> gconv -> g) flows
-    through dg and the autograd graph of xs as usual."""
+    through dg and the autograd graph of xs as usual.
+
+    xs: the caller's already-computed seqsum_permute(obs) (the model has it as
+    the gconv input), else it is computed here. node_major: the output is
+    (B, N, T, C), the sequence layout the RNN reads, and the incoming gradient
+    is taken in that layout, so no permute copy runs in either direction.
+    dw / db come out of gate_bwd summed over the batch and rounded; dobs is
+    neither computed nor stored when obs needs no gradient."""
 
     @staticmethod
-    def forward(ctx, obs, g, fcw, fcb):
+    def forward(ctx, obs, g, fcw, fcb, xs=None, node_major=False):
         C = require_hip()
         obs = obs.contiguous()
-        with torch.no_grad():
-            xs = C.seqsum_permute(obs)
-        out, z, u, s = C.gate_fwd(obs, g.contiguous(), xs, fcw.to(obs.dtype),
-                                  fcb.to(obs.dtype))
+        if xs is None:
+            with torch.no_grad():
+                xs = C.seqsum_permute(obs)
+        out, z, u, s = C.gate_fwd(obs, g.contiguous(), xs.detach(),
+                                  fcw.to(obs.dtype), fcb.to(obs.dtype),
+                                  node_major)
         ctx.save_for_backward(obs, fcw, z, u, s)
+        ctx.node_major = node_major
         return out
 
     @staticmethod
     def backward(ctx, dout):
         C = require_hip()
         obs, fcw, z, u, s = ctx.saved_tensors
-        dobs, dg, dw_part, db_part = C.gate_bwd(dout, obs, fcw.to(obs.dtype), z, u, s)
-        dw = dw_part.sum(dim=0).to(fcw.dtype)
-        db = db_part.sum(dim=0).to(fcw.dtype)
-        return dobs, dg, dw, db
+        dobs, dg, dw, db, dw_f, db_f = C.gate_bwd(
+            dout, obs, fcw.to(obs.dtype), z, u, s, ctx.node_major,
+            ctx.needs_input_grad[0])
+        if fcw.dtype != obs.dtype:
+            dw, db = dw_f.to(fcw.dtype), db_f.to(fcw.dtype)
+        return dobs, dg, dw, db, None, None
 
 
 class HeadFn(torch.autograd.Function):
@@ -428,6 +475,9 @@ class HeadFn(torch.autograd.Function):
         dfeat = C.head_bwd(dy, fc_weight.view(-1).to(dy.dtype), G)
         # dw = dy^T fsum, db = sum(dy) as one reduction kernel (the last
         # library GEMM on the step was exactly this 1xG tall-skinny)
+        if fc_weight.dtype == dy.dtype:   # rounded by the kernel itself
+            dw, db = C.head_wgrad_grads(dy, fsum)
+            return (dw, db) + (dfeat,) * ctx.M
         dwf, dbf = C.head_wgrad(dy, fsum)
         dw = dwf.view(1, G).to(fc_weight.dtype)
         db = dbf.to(fc_weight.dtype)
