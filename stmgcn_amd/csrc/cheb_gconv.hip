@@ -120,9 +120,9 @@ cheb_fused_fwd_kernel(const int* __restrict__ rowptr,
   if constexpr (MF) {
     const GcLane l;
     if (l.wv < (Cout >> 4)) {          // wave wv owns output cols [16wv,16wv+16)
-      gc_f32x4 acc[2];
-      acc[0] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
-      acc[1] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 acc[2];
+      acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
       gc_mix_mfma<T>(lds, W, kofs, C, Cout, l, acc);
       if (x0 != nullptr) gc_mix_mfma<T>(l0, W, 0, C, Cout, l, acc);
       gc_y_store_frag<T>(acc, b, n0, N, Cout, l, bias, yacc, yout, first, act);
@@ -218,7 +218,7 @@ extern "C" void stmgcn_spmm_step(
     float alpha, float beta, float gamma) {
   const int rows_per_block = (C <= 256) ? (256 / C > 0 ? 256 / C : 1) : 1;
   const dim3 grid((N + rows_per_block - 1) / rows_per_block, B);
-  gc_dispatch_dtype(dtype, [&](auto t) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL((spmm_step_kernel<T>), grid, dim3(256), 0,
                        (hipStream_t)stream_v, rowptr, colidx, vals,
@@ -230,14 +230,14 @@ extern "C" void stmgcn_spmm_step(
 
 extern "C" void stmgcn_cheb_fused_fwd_step(void* stream_v, int dtype,
                                            const ChebFwdArgs& a) {
-  gc_dispatch_dtype(dtype, [&](auto t) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
     launch_fused_fwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }
 
 extern "C" void stmgcn_cheb_fused_bwd_step(void* stream_v, int dtype,
                                            const ChebBwdArgs& a) {
-  gc_dispatch_dtype(dtype, [&](auto t) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
     launch_fused_bwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }

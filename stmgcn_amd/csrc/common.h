@@ -4,6 +4,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
 #include "kernels.h"  // entry-point prototypes, argument structs, SEQ_TILE
 
 #define STM_WAVE 64  // CDNA wavefront width (never 32)
@@ -24,6 +26,57 @@ template <> __device__ __forceinline__ __hip_bfloat16 fromF<__hip_bfloat16>(floa
   return __float2bfloat16(v);
 }
 template <> __device__ __forceinline__ __half fromF<__half>(float v) { return __float2half(v); }
+
+// ---------------------------------------------------------------------------
+// Host-side dtype dispatch: f(T{}) for the element type of a StmDtype code, so
+// a launcher writes each launch once inside a generic lambda
+// ([&](auto t) { using T = decltype(t); ... }). A code outside the enum
+// launches nothing (bindings.cpp admits only these three).
+template <typename F> void stm_dispatch_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case STM_F32: f(float{}); break;
+    case STM_BF16: f(__hip_bfloat16{}); break;
+    case STM_F16: f(__half{}); break;
+  }
+}
+// The same for kernels that have no fp32 form (MFMA fragments, packed 16 B
+// moves): any other code is reported under the entry point's name `who`.
+template <typename F> void stm_dispatch_lowp(const char* who, int dtype, F&& f) {
+  switch (dtype) {
+    case STM_BF16: f(__hip_bfloat16{}); break;
+    case STM_F16: f(__half{}); break;
+    default: printf("%s: unsupported dtype %d (bf16/f16 only)\n", who, dtype);
+  }
+}
+// A runtime flag as a template argument: f(std::true_type{}) or
+// f(std::false_type{}); the kernel takes decltype(flag)::value.
+template <typename F> void stm_dispatch_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// ---------------------------------------------------------------------------
+// MFMA fragment vocabulary of v_mfma_f32_16x16x32_{bf16,f16}: a lane's 8-wide
+// A/B operand and 4-wide fp32 C/D accumulator (lane maps: mfma_probe_kernel,
+// fused_rnn.hip). Frag8<float> exists only so that templates which also serve
+// the gconv scalar (fp32) path can name the types; it feeds no MFMA.
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+template <typename T> struct Frag8 { using type = float; using elem = float; };
+template <> struct Frag8<__hip_bfloat16> { using type = bf16x8; using elem = __bf16; };
+template <> struct Frag8<__half> { using type = f16x8; using elem = _Float16; };
+
+__device__ __forceinline__ float elemF(__bf16 v) { return (float)v; }
+__device__ __forceinline__ float elemF(_Float16 v) { return (float)v; }
+
+__device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma16x16x32(f16x8 a, f16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
 
 // Fast device transcendentals: v_exp_f32 + v_rcp_f32 (~1 ulp each) instead
 // of libm tanhf (~30 VALU instr) / IEEE divide — the RNN pointwise phase is

@@ -75,9 +75,9 @@ dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
   if constexpr (MF) {
     const GcLane l;
     if (l.wv < (Cout >> 4)) {          // wave wv owns output cols [16wv,16wv+16)
-      gc_f32x4 acc[2];
-      acc[0] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
-      acc[1] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 acc[2];
+      acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
       gc_mix_mfma<T>(lf, W, kofs_f, C, Cout, l, acc);
       gc_mix_mfma<T>(lb, W, kofs_b, C, Cout, l, acc);
       if (x0 != nullptr) gc_mix_mfma<T>(l0, W, 0, C, Cout, l, acc);
@@ -188,7 +188,7 @@ void launch_dual_bwd(hipStream_t st, const DualBwdArgs& a) {
 // are instantiated — and C <= 64, Cout <= 64.
 extern "C" void stmgcn_dual_fused_fwd_step(void* stream_v, int dtype,
                                            const DualFwdArgs& a) {
-  gc_dispatch_dtype(dtype, [&](auto t) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     if constexpr (!std::is_same<T, float>::value)
       launch_dual_fwd<T>((hipStream_t)stream_v, a);
@@ -197,7 +197,7 @@ extern "C" void stmgcn_dual_fused_fwd_step(void* stream_v, int dtype,
 
 extern "C" void stmgcn_dual_fused_bwd_step(void* stream_v, int dtype,
                                            const DualBwdArgs& a) {
-  gc_dispatch_dtype(dtype, [&](auto t) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
     if constexpr (!std::is_same<T, float>::value)
       launch_dual_bwd<T>((hipStream_t)stream_v, a);

@@ -15,26 +15,25 @@
 //   4 waves; wave w owns gate-channel slice [16w, 16w+16) of each of the
 //   4 (LSTM) / 3 (GRU) gate types -> i/f/g/o for one (seq,channel) pair land
 //   in the SAME lane's accumulators, making the cell update lane-local.
-//   M = 64 sequences = 4 MFMA row-tiles; K = H (+C for layers > 0) chunked
-//   by 32. Weights are loaded once per layer into VGPR B-fragments
-//   (contiguous 16B per lane from the (4H, H|C) row-major weight).
+//   M = SEQ_TILE = 32 sequences = 2 MFMA row-tiles (at 64 rows the forward
+//   needed 230 VGPR + 68 AGPR, one wave per SIMD; 32 rows fit two workgroups
+//   per CU); K = H (+C for layers > 0) chunked by 32. Weights are loaded once
+//   per layer into VGPR B-fragments (contiguous 16B per lane from the
+//   (4H, H|C) row-major weight).
+//
+// Hand-offs between layers ride global memory, never LDS: forward writes each
+// layer's hidden sequence to hseq_g (natural (S_pad, H) order, staged through
+// the live LDS slot) and the next layer reads it back; backward passes the
+// gradient w.r.t. that sequence through dh_g in fragment-native order.
 //
 // Saves for BPTT (training): per (layer, t): post-activation gates + cell
-// state in fragment-native order (coalesced 16B/lane), and the hidden
-// sequence in natural (S_pad, H) order staged through LDS.
+// state in fragment-native order (coalesced 16B/lane), plus hseq_g.
 //
 // fp32/fp64 paths are not served here: bf16/f16 in, fp32 accumulate.
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// 32-row sequence tiles: MT=2 m-tiles/wave halves per-wave register state
-// vs the original 64-row tiles (fwd was 230 VGPR + 68 AGPR -> occupancy 1
-// wave/SIMD; 32-row tiles fit 2 workgroups/CU, hiding LDS/MFMA latency).
-// SEQ_TILE (= 32) lives in common.h next to the dA tile layout it fixes.
+// SEQ_TILE (= 32) lives in kernels.h; common.h fixes the dA tile layout on it.
 #define RNN_H 64
 static_assert(4 * RNN_H == STM_DA_GATES, "dA tile layout assumes 4H = 256");
 #define MAX_LAYERS 8
@@ -47,22 +46,8 @@ struct RnnPtrs {
   const void* b_hh[MAX_LAYERS];   // (G*H,) model dtype
 };
 
-// (LDS swizzle lds_swz for 128 B tile rows lives in common.h — shared with
-// the fused ChebConv kernels.)
-
-template <typename T> struct Frag8;
-template <> struct Frag8<__hip_bfloat16> { using type = bf16x8; using elem = __bf16; };
-template <> struct Frag8<__half> { using type = f16x8; using elem = _Float16; };
-
-__device__ __forceinline__ float elemF(__bf16 v) { return (float)v; }
-__device__ __forceinline__ float elemF(_Float16 v) { return (float)v; }
-
-__device__ __forceinline__ f32x4 mfma16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16x16x32(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
+// (The MFMA fragment types, mfma16x16x32 and the LDS swizzle lds_swz for
+// 128 B tile rows live in common.h — shared with the wgrad and gconv kernels.)
 
 // ---------------------------------------------------------------------------
 // MFMA layout probe (validated on hardware by tests/test_gpu_kernels.py):
@@ -108,8 +93,8 @@ extern "C" __global__ void mfma_probe_kernel(const __hip_bfloat16* A,
 // mandatory (the wgrad kernel consumes hseq_g), so the hand-off is free and
 // LDS drops from (2*Tst+eps) slots (64 KB at T=8 -> 2 workgroups/CU) to
 // 2 slots (~8.5 KB -> occupancy is register-bound at 4 waves/SIMD instead).
-// CIN1 additionally stages the scalar input sequence ([Tst][ST] T).
-template <typename T, bool CIN1, bool GRU, int ST>
+// CIN1 additionally stages the scalar input sequence ([Tst][SEQ_TILE] T).
+template <typename T, bool CIN1, bool GRU>
 __global__ void __launch_bounds__(256, 2)
 lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
                 T* __restrict__ out,        // (S, H) or (S, Tst, H)
@@ -121,15 +106,15 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
                 RnnPtrs ptrs,
                 int S, int Tst, int L, int ret_seq) {
   using frag = typename Frag8<T>::type;
-  constexpr int MT = ST / 16;        // MFMA row-tiles per wave
-  constexpr int SLOT = ST * 128;     // one timestep LDS slot, bytes
+  constexpr int MT = SEQ_TILE / 16;        // MFMA row-tiles per wave
+  constexpr int SLOT = SEQ_TILE * 128;     // one timestep LDS slot, bytes
   extern __shared__ char lds[];
-  const int s0 = blockIdx.x * ST;
+  const int s0 = blockIdx.x * SEQ_TILE;
   const int wv = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int l16 = lane & 15;
   const int lgrp = lane >> 4;
-  const long S_pad = (long)gridDim.x * ST;
+  const long S_pad = (long)gridDim.x * SEQ_TILE;
 
   // ping/pong h slots by t parity (explicit ternary: an LDS-pointer array
   // initializer is rejected by the AMDGPU backend)
@@ -138,11 +123,11 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
 
   // ---- stage scalar input x into LDS (CIN1 only) -------------------------
   if (CIN1) {
-    for (int i = threadIdx.x; i < ST * Tst; i += 256) {
-      const int s = i % ST, t = i / ST;
+    for (int i = threadIdx.x; i < SEQ_TILE * Tst; i += 256) {
+      const int s = i % SEQ_TILE, t = i / SEQ_TILE;
       T v = fromF<T>(0.f);
       if (s0 + s < S) v = x[(long)(s0 + s) * Tst + t];
-      ((T*)xbuf)[t * ST + s] = v;
+      ((T*)xbuf)[t * SEQ_TILE + s] = v;
     }
     __syncthreads();
   }
@@ -260,7 +245,7 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
         if (CIN1 && layer == 0)
           #pragma unroll
           for (int r = 0; r < 4; ++r)
-            xv[r] = toF<T>(((const T*)xbuf)[t * ST + 16 * m + 4 * lgrp + r]);
+            xv[r] = toF<T>(((const T*)xbuf)[t * SEQ_TILE + 16 * m + 4 * lgrp + r]);
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float gi = acc[m][0][r] + bias[0];
@@ -321,7 +306,7 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
                 + (long)s0 * RNN_H;
         const bool keep_h = (layer < L - 1) || (gates_g != nullptr);
         char* slot = hslot(t);
-        for (int i = threadIdx.x; i < ST * 8; i += 256) {
+        for (int i = threadIdx.x; i < SEQ_TILE * 8; i += 256) {
           const int c8 = i & 7, sr = i >> 3;
           frag v = *(frag*)&slot[lds_swz(sr, c8 * 16)];
           if (keep_h) *(frag*)&hp[sr * RNN_H + c8 * 8] = v;
@@ -339,7 +324,7 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
         const long base = ((long)layer * Tst + t);
         // gates: (L,Tst, S_pad*4H) as [wave][m][lane][16] T
         T* gp = gates_g + base * (S_pad * 4 * RNN_H)
-                + (long)blockIdx.x * (ST * 4 * RNN_H)
+                + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H)
                 + ((wv * MT) * 64) * 16;
         #pragma unroll
         for (int m = 0; m < MT; ++m)
@@ -349,7 +334,7 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
         // (LSTM: c_t; GRU: h_{t-1}) — T-typed save halves HBM traffic vs
         // fp32; bwd tolerances cover the rounding (tests at 8% rel)
         T* cp = cseq_g + base * (S_pad * RNN_H)
-                + (long)blockIdx.x * (ST * RNN_H) + (wv * MT) * 64 * 4;
+                + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
         #pragma unroll
         for (int m = 0; m < MT; ++m) {
           T c4[4];
@@ -366,44 +351,45 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
   }
 }
 
-template <typename T>
-void launch_fwd(hipStream_t stream, const void* x, void* out, void* hseq_g,
-                void* cseq_g, void* gates_g, const RnnPtrs& ptrs, int S,
-                int Tst, int L, int cin, int ret_seq, int gru) {
-  constexpr int ST = SEQ_TILE;
-  const int nblk = (S + ST - 1) / ST;
-  const bool cin1 = (cin == 1);
-  const size_t slot = (size_t)ST * 128;
-  const size_t lds_bytes = 2 * slot + (cin1 ? Tst * ST * sizeof(T) : 0);
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds_bytes, stream,
-                       (const T*)x, (T*)out, (T*)hseq_g, (T*)cseq_g,
-                       (T*)gates_g, ptrs, S, Tst, L, ret_seq);
-  };
-  if (cin1 && !gru) go(lstm_fwd_kernel<T, true, false, ST>);
-  else if (cin1 && gru) go(lstm_fwd_kernel<T, true, true, ST>);
-  else if (!gru) go(lstm_fwd_kernel<T, false, false, ST>);
-  else go(lstm_fwd_kernel<T, false, true, ST>);
+// Per-layer pointer tables of one launch; the backward passes no biases.
+static RnnPtrs rnn_ptrs(int L, const void** w_ih, const void** w_hh,
+                        const void** b_ih, const void** b_hh) {
+  RnnPtrs p{};
+  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
+    p.w_ih[l] = w_ih[l]; p.w_hh[l] = w_hh[l];
+    p.b_ih[l] = b_ih ? b_ih[l] : nullptr;
+    p.b_hh[l] = b_hh ? b_hh[l] : nullptr;
+  }
+  return p;
 }
 
-extern "C" void stmgcn_lstm_fwd(void* stream_v, int dtype, const void* x,
+// f(CIN1, GRU) as std::bool_constant values: the kernel variant of a launch
+template <typename F> void rnn_dispatch_variant(int cin, int gru, F&& f) {
+  stm_dispatch_bool(cin == 1, [&](auto cin1) {
+    stm_dispatch_bool(gru != 0, [&](auto is_gru) { f(cin1, is_gru); });
+  });
+}
+
+extern "C" void stmgcn_lstm_fwd(void* stream, int dtype, const void* x,
                                 void* out, void* hseq_g, void* cseq_g,
                                 void* gates_g, const void** w_ih,
                                 const void** w_hh, const void** b_ih,
                                 const void** b_hh, int S, int Tst, int L,
                                 int cin, int ret_seq, int gru) {
-  RnnPtrs p;
-  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
-    p.w_ih[l] = w_ih[l]; p.w_hh[l] = w_hh[l];
-    p.b_ih[l] = b_ih[l]; p.b_hh[l] = b_hh[l];
-  }
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (dtype == STM_BF16)
-    launch_fwd<__hip_bfloat16>(stream, x, out, hseq_g, cseq_g, gates_g, p, S,
-                               Tst, L, cin, ret_seq, gru);
-  else if (dtype == STM_F16)
-    launch_fwd<__half>(stream, x, out, hseq_g, cseq_g, gates_g, p, S, Tst, L,
-                       cin, ret_seq, gru);
+  const RnnPtrs p = rnn_ptrs(L, w_ih, w_hh, b_ih, b_hh);
+  const int nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
+  stm_dispatch_lowp("stmgcn_lstm_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    // two h slots + the CIN1 scalar input stage
+    const size_t lds_bytes =
+        2 * SEQ_TILE * 128 + (cin == 1 ? Tst * SEQ_TILE * sizeof(T) : 0);
+    rnn_dispatch_variant(cin, gru, [&](auto cin1, auto is_gru) {
+      hipLaunchKernelGGL(
+          (lstm_fwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>),
+          dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)x,
+          (T*)out, (T*)hseq_g, (T*)cseq_g, (T*)gates_g, p, S, Tst, L, ret_seq);
+    });
+  });
 }
 
 extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
@@ -420,16 +406,13 @@ extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
 // reverse. Per step the pointwise phase turns (dh, dc, saved gates, saved
 // cell) into gate-preactivation grads dA — lane-local in the MFMA fragment
 // layout — then two MFMA GEMMs produce dh_{t-1} (recurrent carry, kept in
-// registers) and dx_t (written into the dh hand-off LDS slot for the layer
+// registers) and dx_t (written to the global dh_g hand-off for the layer
 // below, or to the dx output at layer 0). dA is also streamed to global in
 // the tiled wgrad-fragment order documented in common.h (each lane's 8
 // values per gate slot are one 16 B store straight from the pointwise
 // registers); lstm_wgrad_kernel (wgrad.hip) then forms all weight gradients
 // dW = dA^T @ [h_prev | x] in one launch, which keeps this kernel lean (no
 // long-lived dW accumulators).
-
-// dA stream store placement in lstm_bwd_kernel (see the pointwise phase)
-constexpr bool kDaStoreEarly = false;
 
 __device__ __forceinline__ int swzA(int s, int cbyte) {      // dA rows: 512 B
   return s * 512 + (cbyte ^ ((s & 15) << 4));
@@ -440,7 +423,7 @@ __device__ __forceinline__ int swzA(int s, int cbyte) {      // dA rows: 512 B
 // dA = [dr_pre, dz_pre, dn_pre, dBn] so the dgrad GEMMs against the packed
 // transposed weights and the batched wgrad kernel run unchanged. The direct
 // dh_{t-1} += dh_t * z term rides the dc[][] register carry.
-template <typename T, bool CIN1, bool GRU, int ST>
+template <typename T, bool CIN1, bool GRU>
 __global__ void __launch_bounds__(256, 2)
 lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
                 const T* __restrict__ x,        // (S,Tst,Cin)
@@ -454,15 +437,14 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
                 int S, int Tst, int L, int ret_seq) {
   using frag = typename Frag8<T>::type;
   using elem = typename Frag8<T>::elem;
-  constexpr int MT = ST / 16;
-  static_assert(ST == SEQ_TILE, "one workgroup emits exactly one dA tile per step");
+  constexpr int MT = SEQ_TILE / 16;
   extern __shared__ char lds[];
-  const int s0 = blockIdx.x * ST;
+  const int s0 = blockIdx.x * SEQ_TILE;
   const int wv = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int l16 = lane & 15;
   const int lgrp = lane >> 4;
-  const long S_pad = (long)gridDim.x * ST;
+  const long S_pad = (long)gridDim.x * SEQ_TILE;
   const int hch = 16 * wv + l16;
 
   // LDS holds only the dA tiles (ping/pong by timestep parity: the pointwise
@@ -471,13 +453,13 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   // cross-layer dh hand-off lives in GLOBAL scratch dh_g — dropping the
   // [Tst] dh slots cuts LDS from ~64.5 KB (2 WGs/CU) to ~32.5 KB (4 WGs/CU),
   // doubling the occupancy that hides the serial BPTT latency.
-  char* dA_buf0 = lds;                        // [ST][512B] swizzled
-  char* dA_buf1 = dA_buf0 + ST * 512;
-  float* red = (float*)(dA_buf1 + ST * 512);  // [4][ST] cross-wave scratch
+  char* dA_buf0 = lds;                        // [SEQ_TILE][512B] swizzled
+  char* dA_buf1 = dA_buf0 + SEQ_TILE * 512;
+  float* red = (float*)(dA_buf1 + SEQ_TILE * 512);  // [4][SEQ_TILE] cross-wave scratch
   // lane-PRIVATE gates staging (each lane writes exactly the 2*MT fragments
   // it alone reads next stage -> no cross-wave visibility, no barrier, and
   // the prefetched tile costs LDS instead of 32 live VGPRs)
-  char* gstage = (char*)(red + 4 * ST);       // [256][MT*32B]
+  char* gstage = (char*)(red + 4 * SEQ_TILE);       // [256][MT*32B]
 
   for (int layer = L - 1; layer >= 0; --layer) {
     const bool l0cin1 = CIN1 && layer == 0;
@@ -495,18 +477,18 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
     const long lay_base = (long)layer * Tst;
     auto g_at = [&](int t) {
       return gates_g + (lay_base + t) * (S_pad * 4 * RNN_H)
-             + (long)blockIdx.x * (ST * 4 * RNN_H) + (wv * MT) * 64 * 16;
+             + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H) + (wv * MT) * 64 * 16;
     };
     auto c_at = [&](int t) {
       return cseq_g + (lay_base + t) * (S_pad * RNN_H)
-             + (long)blockIdx.x * (ST * RNN_H) + (wv * MT) * 64 * 4;
+             + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
     };
     // dh hand-off is FRAG-NATIVE: the GEMM2 writer and the pointwise reader
     // use the identical lane mapping (row 16m+4lgrp+r, col hch), so each
     // lane stores/loads its 4 values as one packed 8-byte word.
     auto dh_at = [&](int t) {
       return dh_g + (long)t * (S_pad * RNN_H)
-             + (long)blockIdx.x * (ST * RNN_H) + (wv * MT) * 64 * 4;
+             + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
     };
     char* gmine = gstage + threadIdx.x * (MT * 32);
     #pragma unroll
@@ -615,22 +597,14 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       }
       // ---- dA stream for the wgrad kernel, tile order (common.h): the lane's
       // 4 x 16 B pieces; a wave's store per gate slot covers 1 KiB contiguous.
-      // kDaStoreEarly: store straight from the pointwise registers, before
-      // the barrier. Measured ~1% slower than the end-of-stage store (the
-      // first weight-fragment wait of GEMM1 then also drains these stores —
-      // vmcnt retires in order — on the serial dh_prev path). Default: park
-      // the pieces in the lane-private gates slot, which is dead from here
-      // until the end-of-stage stage-in (exactly 64 B per lane), and store
-      // after the GEMMs, where the next drain is a whole pointwise phase away.
+      // The pieces are parked in the lane-private gates slot, which is dead
+      // from here until the end-of-stage stage-in (exactly 64 B per lane), and
+      // stored after the GEMMs. A store issued here would be drained by GEMM1's
+      // first weight-fragment wait (vmcnt retires in order) on the serial
+      // dh_prev path: ~1% slower, profiles/r03_da_stream_layout.md.
       T* out_dA = dA_g + stm_da_tile_off(base * S_pad + s0);
       #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (kDaStoreEarly)
-          *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
-              *(const frag*)pk[q];
-        else
-          *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
-      }
+      for (int q = 0; q < 4; ++q) *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
       __syncthreads();   // dA visible to all waves
 
       // prefetch next stage's saves (overlap the GEMMs below). The gate
@@ -682,7 +656,7 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
           for (int r = 0; r < 4; ++r) dh_rec[m][r] = acc[m][r];
       }
 
-      // ---- GEMM2: dx = dA @ W_ih -> dh_lds slot t / dx output ------------
+      // ---- GEMM2: dx = dA @ W_ih -> dh_g step t / dx output --------------
       if (!l0cin1) {
         f32x4 acc[MT];
         #pragma unroll
@@ -723,12 +697,12 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
             float v = dxpart[m][r];
             #pragma unroll
             for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off, 64);
-            if (l16 == 0) red[wv * ST + 16 * m + 4 * lgrp + r] = v;
+            if (l16 == 0) red[wv * SEQ_TILE + 16 * m + 4 * lgrp + r] = v;
           }
         __syncthreads();
         if (wv == 0) {
-          for (int sA = lane; sA < ST; sA += 64) {
-            const float v = red[sA] + red[ST + sA] + red[2 * ST + sA] + red[3 * ST + sA];
+          for (int sA = lane; sA < SEQ_TILE; sA += 64) {
+            const float v = red[sA] + red[SEQ_TILE + sA] + red[2 * SEQ_TILE + sA] + red[3 * SEQ_TILE + sA];
             if (s0 + sA < S) dx[(long)(s0 + sA) * Tst + t] = fromF<T>(v);
           }
         }
@@ -736,12 +710,10 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
 
       // ---- stream the parked dA pieces to global (4 x ds_read_b128 of the
       // lane's own slot; no cross-lane traffic, no barrier) ------------------
-      if (!kDaStoreEarly) {
-        #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
-              *(const frag*)&gmine[q * 16];
-      }
+      #pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
+            *(const frag*)&gmine[q * 16];
 
       if (t > 0) {
         #pragma unroll
@@ -757,349 +729,27 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   }  // layer loop
 }
 
-
-// ===========================================================================
-// WAVE-PRIVATE BPTT backward (round-2 experiment, STMGCN_BWD_WAVE=1).
-//
-// The classic lstm_bwd_kernel couples its 4 waves every stage: the
-// pointwise phase writes dA columns that OTHER waves' GEMMs consume, so a
-// __syncthreads sits on the serial BPTT critical path 24 times per block —
-// measured 71% wave-park at occupancy 2 (profiles/r02_pmc_sq_waits.md).
-//
-// This variant gives each WAVE 16 sequences end-to-end: pointwise (in the
-// MFMA D-fragment layout, which is ALSO the forward save layout, so gates/
-// cell bundles arrive as coalesced 16 B fragments), a wave-private LDS
-// transpose of dA into A-fragment layout, and both GEMMs over the full
-// k = 4H and n = H ranges per wave. Nothing crosses waves: there are ZERO
-// barriers in the kernel, the cross-layer dh hand-off is packed so the
-// writing lane is the reading lane (plain vmcnt ordering suffices), and a
-// 64-row block doubles the rows in flight per CU at the same occupancy.
-//
-// Geometry: 256 threads = 4 waves; wave w owns rows [64*blockIdx + 16w ..
-// +16). D-layout per lane: rows 16w + 4*lgrp + r (r 0..3), channels
-// 16*nt + l16 (nt 0..3). Forward saved its bundles from 32-row blocks with
-// channel-sliced waves; the (block, m, wave, lane) coordinates of this
-// wave's rows are bxf = row0/32, mf = (row0/16)&1, wv_f = nt, lane_f = lane
-// — the SAME lane index, so every gates/cseq access is a direct fragment
-// load of the forward's save.
-template <typename T, bool CIN1, bool GRU>
-__global__ void __launch_bounds__(256, 2)
-lstm_bwd_wave_kernel(const T* __restrict__ dout,    // (S,H) or (S,Tst,H)
-                     const T* __restrict__ cseq_g,  // fwd save (see fwd)
-                     const T* __restrict__ gates_g, // fwd save
-                     RnnPtrs w,                     // w_ih/w_hh TRANSPOSED (C|H, 4H)
-                     T* __restrict__ dx,            // (S,Tst,Cin)
-                     T* __restrict__ dA_g,          // (L,Tst,S_pad,4H) tiled
-                     T* __restrict__ dh_g,          // (Tst*S_pad*H) packed scratch
-                     int S, int S_pad, int Tst, int L, int ret_seq) {
-  using frag = typename Frag8<T>::type;
-  using elem = typename Frag8<T>::elem;
-  extern __shared__ char lds[];
-  const int wv = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int l16 = lane & 15;
-  const int lgrp = lane >> 4;
-  const int row0 = blockIdx.x * 64 + 16 * wv;     // wave's first row
-  if (row0 >= S_pad) return;                       // whole-wave tail guard
-
-  char* dAw = lds + wv * 8192;                     // wave-private dA (16x512B)
-  char* gmine = lds + 32768 + threadIdx.x * 128;   // lane-private gates stage
-
-  const int bxf = row0 >> 5;                       // fwd 32-row block
-  const int mf = (row0 >> 4) & 1;                  // fwd m-tile
-
-  for (int layer = L - 1; layer >= 0; --layer) {
-    const bool l0cin1 = CIN1 && layer == 0;
-    const T* WhhT = (const T*)w.w_hh[layer];       // (H, 4H)
-    const T* WihT = (const T*)w.w_ih[layer];       // (Cin_l, 4H)
-    const long lay_base = (long)layer * Tst;
-    // fwd-save bundle addresses for this lane (16 gate T / 4 cell T per nt)
-    auto g_at = [&](int t, int nt) {
-      return gates_g + (lay_base + t) * ((long)S_pad * 4 * RNN_H)
-             + (long)bxf * (32 * 4 * RNN_H) + nt * (2 * 64 * 16)
-             + (mf * 64 + lane) * 16;
-    };
-    auto c_at = [&](int t, int nt) {
-      return cseq_g + (lay_base + t) * ((long)S_pad * RNN_H)
-             + (long)bxf * (32 * RNN_H) + nt * (2 * 64 * 4)
-             + (mf * 64 + lane) * 4;
-    };
-    // packed lane-private dh hand-off (writer lane == reader lane)
-    auto dh_at = [&](int t) {
-      return dh_g + (long)t * ((long)S_pad * RNN_H)
-             + (long)blockIdx.x * (64 * RNN_H) + wv * (16 * RNN_H) + lane * 16;
-    };
-
-    float dh_rec[4][4], dc[4][4];                  // [nt][r], D-layout
-    #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) { dh_rec[nt][r] = 0.f; dc[nt][r] = 0.f; }
-
-    float wihv[4][4];                              // [q][nt] this lane's W_ih column
-    if (l0cin1)
-      #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        #pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          wihv[q][nt] = toF<T>(WihT[q * 64 + 16 * nt + l16]);
-
-    // ---- stage-in for t = Tst-1: gates -> lane LDS, c/dh -> registers ----
-    #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      *(frag*)&gmine[nt * 32 + 0] = *(((const frag*)g_at(Tst - 1, nt)) + 0);
-      *(frag*)&gmine[nt * 32 + 16] = *(((const frag*)g_at(Tst - 1, nt)) + 1);
-    }
-    ulong1 cc_t[4], cc_p[4], dhup[4];
-    #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      cc_t[nt] = *(const ulong1*)c_at(Tst - 1, nt);
-      cc_p[nt] = ulong1{0};
-      if (!GRU && Tst >= 2) cc_p[nt] = *(const ulong1*)c_at(Tst - 2, nt);
-    }
-    if (layer < L - 1) {
-      #pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-        dhup[nt] = *(((const ulong1*)dh_at(Tst - 1)) + nt);
-    }
-
-    for (int t = Tst - 1; t >= 0; --t) {
-      // ---- pointwise in D-layout; dA transposed through wave LDS --------
-      float dxacc[4];                              // [r] (CIN1 l0 only)
-      if (l0cin1) { dxacc[0] = dxacc[1] = dxacc[2] = dxacc[3] = 0.f; }
-      T* out_dA = dA_g + stm_da_tile_off((lay_base + t) * (long)S_pad
-                                         + (long)bxf * SEQ_TILE);
-      #pragma unroll 1
-      for (int nt = 0; nt < 4; ++nt) {             // serialized: live-range cap
-        alignas(8) T pk[4][4];                     // [slot q][r] stream pieces
-        frag gf0 = *(const frag*)&gmine[nt * 32 + 0];   // [i r0..3 | f r0..3]
-        frag gf1 = *(const frag*)&gmine[nt * 32 + 16];  // [g r0..3 | o r0..3]
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = row0 + 4 * lgrp + r;
-          float dh = dh_rec[nt][r];
-          if (layer < L - 1) {
-            dh += elemF(((elem*)&dhup[nt])[r]);
-          } else if (ret_seq) {
-            if (row < S)
-              dh += toF<T>(dout[((long)row * Tst + t) * RNN_H + 16 * nt + l16]);
-          } else if (t == Tst - 1) {
-            if (row < S)
-              dh += toF<T>(dout[(long)row * RNN_H + 16 * nt + l16]);
-          }
-          const float ctv = elemF(((elem*)&cc_t[nt])[r]);
-          float dAi, dAf, dAg, dAo;
-          if (GRU) {
-            const float r_ = elemF(gf0[r]);
-            const float z_ = elemF(gf0[4 + r]);
-            const float n_ = elemF(gf1[r]);
-            const float Bn = elemF(gf1[4 + r]);
-            const float hprev = ctv;               // GRU save = h_{t-1}
-            dh += dc[nt][r];
-            const float dz_pre = dh * (hprev - n_) * z_ * (1.f - z_);
-            const float dn_pre = dh * (1.f - z_) * (1.f - n_ * n_);
-            dAo = dn_pre * r_;                     // dBn
-            dAi = dn_pre * Bn * r_ * (1.f - r_);   // dr_pre
-            dAf = dz_pre;
-            dAg = dn_pre;
-            dc[nt][r] = dh * z_;
-          } else {
-            const float i_ = elemF(gf0[r]);
-            const float f_ = elemF(gf0[4 + r]);
-            const float g_ = elemF(gf1[r]);
-            const float o_ = elemF(gf1[4 + r]);
-            const float cpv = (t > 0) ? elemF(((elem*)&cc_p[nt])[r]) : 0.f;
-            const float tc = stm_tanh(ctv);
-            float dcv = dc[nt][r] + dh * o_ * (1.f - tc * tc);
-            dAo = dh * tc * o_ * (1.f - o_);
-            dAi = dcv * g_ * i_ * (1.f - i_);
-            dAf = dcv * cpv * f_ * (1.f - f_);
-            dAg = dcv * i_ * (1.f - g_ * g_);
-            dc[nt][r] = dcv * f_;
-          }
-          const int rl = 4 * lgrp + r;             // wave-local row
-          const int ch = 16 * nt + l16;
-          pk[0][r] = fromF<T>(dAi);
-          pk[1][r] = fromF<T>(dAf);
-          pk[2][r] = fromF<T>(dAg);
-          pk[3][r] = fromF<T>(dAo);
-          #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *(T*)&dAw[swzA(rl, (q * 64 + ch) * 2)] = pk[q][r];
-          if (l0cin1)
-            dxacc[r] += dAi * wihv[0][nt] + dAf * wihv[1][nt]
-                      + dAg * wihv[2][nt] + dAo * wihv[3][nt];
-        }
-        // dA stream, tile order (common.h): this wave owns m-tile mf of
-        // tile bxf, so its 4 rows per (slot, channel) are k' = 8*lgrp +
-        // 4*mf + r -> one 8 B piece
-        #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *(ulong1*)&out_dA[stm_da_elem(q * RNN_H + 16 * nt + l16,
-                                        8 * lgrp + 4 * mf)] =
-              *(const ulong1*)pk[q];
-      }
-      // wave-private transpose: in-order LDS, no cross-wave traffic — the
-      // A-fragment reads below only need the implicit lgkmcnt waits (kept
-      // in LDS, re-read per GEMM: 8 extra ds_reads beat 32 live VGPRs)
-      auto a_at = [&](int kk) {
-        return *(const frag*)&dAw[swzA(l16, (kk * 32 + lgrp * 8) * 2)];
-      };
-
-      // ---- prefetch next stage's saves (land during the GEMMs) ----------
-      frag gld[4][2];
-      ulong1 cnext[4], dhnext[4];
-      if (t > 0) {
-        #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          gld[nt][0] = *(((const frag*)g_at(t - 1, nt)) + 0);
-          gld[nt][1] = *(((const frag*)g_at(t - 1, nt)) + 1);
-        }
-        if (GRU || t >= 2) {
-          #pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            cnext[nt] = *(const ulong1*)c_at(GRU ? t - 1 : t - 2, nt);
-        }
-        if (layer < L - 1) {
-          #pragma unroll
-          for (int nt = 0; nt < 4; ++nt)
-            dhnext[nt] = *(((const ulong1*)dh_at(t - 1)) + nt);
-        }
-      }
-
-      // ---- GEMM1: dh_prev = dA @ W_hh (full k=4H, n=H per wave) ---------
-      if (t > 0) {
-        #pragma unroll 2
-        for (int nt = 0; nt < 4; ++nt) {
-          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-          #pragma unroll 4
-          for (int kk = 0; kk < 8; ++kk) {
-            frag b = *(const frag*)&WhhT[(16 * nt + l16) * (4 * RNN_H)
-                                         + kk * 32 + lgrp * 8];
-            acc = mfma16x16x32(a_at(kk), b, acc);
-          }
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) dh_rec[nt][r] = acc[r];
-        }
-      }
-
-      // ---- GEMM2: dx / dh hand-off ---------------------------------------
-      if (!l0cin1) {
-        #pragma unroll 2
-        for (int nt = 0; nt < 4; ++nt) {
-          f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-          #pragma unroll 4
-          for (int kk = 0; kk < 8; ++kk) {
-            frag b = *(const frag*)&WihT[(16 * nt + l16) * (4 * RNN_H)
-                                         + kk * 32 + lgrp * 8];
-            acc = mfma16x16x32(a_at(kk), b, acc);
-          }
-          if (layer > 0) {                         // packed lane-private
-            T v4[4];
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) v4[r] = fromF<T>(acc[r]);
-            *(((ulong1*)dh_at(t)) + nt) = *(ulong1*)v4;
-          } else {                                 // dense dx (S,Tst,64)
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int row = row0 + 4 * lgrp + r;
-              if (row < S)
-                dx[((long)row * Tst + t) * RNN_H + 16 * nt + l16] =
-                    fromF<T>(acc[r]);
-            }
-          }
-        }
-      } else {
-        // CIN1 l0: dx[row,t] = sum_ch dxacc; reduce over the 16 l16 lanes
-        #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = dxacc[r];
-          #pragma unroll
-          for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off, 64);
-          const int row = row0 + 4 * lgrp + r;
-          if (l16 == 0 && row < S) dx[(long)row * Tst + t] = fromF<T>(v);
-        }
-      }
-
-      // ---- stage-end: stage the prefetched gates into lane LDS, rotate --
-      if (t > 0) {
-        #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          *(frag*)&gmine[nt * 32 + 0] = gld[nt][0];
-          *(frag*)&gmine[nt * 32 + 16] = gld[nt][1];
-          cc_t[nt] = GRU ? cnext[nt] : cc_p[nt];
-          if (!GRU) cc_p[nt] = (t >= 2) ? cnext[nt] : ulong1{0};
-          if (layer < L - 1) dhup[nt] = dhnext[nt];
-        }
-      }
-    }  // t loop
-  }  // layer loop
-}
-
-static int bwd_wave_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("STMGCN_BWD_WAVE");
-    mode = e ? atoi(e) : 0;
-  }
-  return mode;
-}
-
-template <typename T>
-void launch_bwd(hipStream_t stream, const void* dout, const void* x,
-                const void* cseq_g, const void* gates_g, const RnnPtrs& w,
-                void* dx, void* dA_g, void* dh_g, int S, int Tst, int L,
-                int cin, int ret_seq, int gru) {
-  constexpr int ST = SEQ_TILE;
-  const int nblk = (S + ST - 1) / ST;
-  const int S_pad = nblk * ST;
-  if (bwd_wave_mode()) {
-    const int nblk64 = (S_pad + 63) / 64;
-    const size_t ldsw = 32768 + 256 * 128;     // wave dA slots + lane gates
-    auto gow = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(nblk64), dim3(256), ldsw, stream,
-                         (const T*)dout, (const T*)cseq_g, (const T*)gates_g,
-                         w, (T*)dx, (T*)dA_g, (T*)dh_g, S, S_pad, Tst, L,
-                         ret_seq);
-    };
-    if (cin == 1 && !gru) gow(lstm_bwd_wave_kernel<T, true, false>);
-    else if (cin == 1 && gru) gow(lstm_bwd_wave_kernel<T, true, true>);
-    else if (!gru) gow(lstm_bwd_wave_kernel<T, false, false>);
-    else gow(lstm_bwd_wave_kernel<T, false, true>);
-    return;
-  }
-  const size_t lds_bytes = 2 * ST * 512 + 4 * ST * sizeof(float)
-                           + 256 * (ST / 16) * 32;   // + lane-private gstage
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds_bytes, stream,
-                       (const T*)dout, (const T*)x, (const T*)cseq_g,
-                       (const T*)gates_g, w, (T*)dx, (T*)dA_g, (T*)dh_g,
-                       S, Tst, L, ret_seq);
-  };
-  if (cin == 1 && !gru) go(lstm_bwd_kernel<T, true, false, ST>);
-  else if (cin == 1 && gru) go(lstm_bwd_kernel<T, true, true, ST>);
-  else if (!gru) go(lstm_bwd_kernel<T, false, false, ST>);
-  else go(lstm_bwd_kernel<T, false, true, ST>);
-}
-
-extern "C" void stmgcn_lstm_bwd(void* stream_v, int dtype, const void* dout,
+extern "C" void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout,
                                 const void* x, const void* cseq_g,
                                 const void* gates_g, const void** w_ihT,
                                 const void** w_hhT, void* dx, void* dA_g,
                                 void* dh_g, int S, int Tst, int L, int cin,
                                 int ret_seq, int gru) {
-  RnnPtrs p;
-  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
-    p.w_ih[l] = w_ihT[l]; p.w_hh[l] = w_hhT[l];
-    p.b_ih[l] = nullptr; p.b_hh[l] = nullptr;
-  }
-  hipStream_t stream = (hipStream_t)stream_v;
-  if (dtype == STM_BF16)
-    launch_bwd<__hip_bfloat16>(stream, dout, x, cseq_g, gates_g, p, dx, dA_g,
-                               dh_g, S, Tst, L, cin, ret_seq, gru);
-  else if (dtype == STM_F16)
-    launch_bwd<__half>(stream, dout, x, cseq_g, gates_g, p, dx, dA_g, dh_g,
-                       S, Tst, L, cin, ret_seq, gru);
+  const RnnPtrs p = rnn_ptrs(L, w_ihT, w_hhT, nullptr, nullptr);
+  const int nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
+  // two dA tiles + the CIN1 dx reduction scratch + the lane-private gstage
+  const size_t lds_bytes = 2 * SEQ_TILE * 512 + 4 * SEQ_TILE * sizeof(float)
+                           + 256 * (SEQ_TILE / 16) * 32;
+  stm_dispatch_lowp("stmgcn_lstm_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    rnn_dispatch_variant(cin, gru, [&](auto cin1, auto is_gru) {
+      hipLaunchKernelGGL(
+          (lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>),
+          dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)dout,
+          (const T*)x, (const T*)cseq_g, (const T*)gates_g, p, (T*)dx,
+          (T*)dA_g, (T*)dh_g, S, Tst, L, ret_seq);
+    });
+  });
 }
 
 // ===========================================================================

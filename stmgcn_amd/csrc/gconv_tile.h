@@ -15,20 +15,7 @@
 
 constexpr int GC_ST = 32;  // graph-node rows per workgroup tile
 
-typedef __attribute__((ext_vector_type(8))) __bf16 gc_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 gc_f16x8;
-typedef __attribute__((ext_vector_type(4))) float gc_f32x4;
-
-template <typename T> struct Frag8 { using type = float; using elem = float; };
-template <> struct Frag8<__hip_bfloat16> { using type = gc_bf16x8; using elem = __bf16; };
-template <> struct Frag8<__half> { using type = gc_f16x8; using elem = _Float16; };
-
-__device__ __forceinline__ gc_f32x4 gc_mfma(gc_bf16x8 a, gc_bf16x8 b, gc_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ gc_f32x4 gc_mfma(gc_f16x8 a, gc_f16x8 b, gc_f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
+// (Frag8, f32x4 and mfma16x16x32 come from common.h.)
 
 // ---- host side: one definition of slot sizes and MFMA eligibility ---------
 // Each launcher uses these for both its dispatch and its LDS byte count.
@@ -53,15 +40,6 @@ template <typename T, typename F> void gc_dispatch_mf(bool mf, F&& f) {
     if (mf) { f(std::true_type{}); return; }
   }
   f(std::false_type{});
-}
-
-// f(T{}) for the element type of a StmDtype code
-template <typename F> void gc_dispatch_dtype(int dtype, F&& f) {
-  switch (dtype) {
-    case STM_F32: f(float{}); break;
-    case STM_BF16: f(__hip_bfloat16{}); break;
-    case STM_F16: f(__half{}); break;
-  }
 }
 
 // ---- device side ----------------------------------------------------------
@@ -120,7 +98,7 @@ struct GcLane {
 template <typename T>
 __device__ __forceinline__ void gc_mix_mfma(const char* __restrict__ slot,
                                             const T* __restrict__ W, int kofs, int C,
-                                            int Cout, GcLane l, gc_f32x4* acc) {
+                                            int Cout, GcLane l, f32x4* acc) {
   using frag = typename Frag8<T>::type;
   using elem = typename Frag8<T>::elem;
   for (int kk = 0; kk < (C >> 5); ++kk) {
@@ -131,8 +109,8 @@ __device__ __forceinline__ void gc_mix_mfma(const char* __restrict__ slot,
           *(const elem*)&W[(kofs + kk * 32 + l.lgrp * 8 + j) * Cout + 16 * l.wv + l.l16];
     frag a0 = *(const frag*)&slot[lds_swz(l.l16, (kk * 32 + l.lgrp * 8) * 2)];
     frag a1 = *(const frag*)&slot[lds_swz(16 + l.l16, (kk * 32 + l.lgrp * 8) * 2)];
-    acc[0] = gc_mfma(a0, bfr, acc[0]);
-    acc[1] = gc_mfma(a1, bfr, acc[1]);
+    acc[0] = mfma16x16x32(a0, bfr, acc[0]);
+    acc[1] = mfma16x16x32(a1, bfr, acc[1]);
   }
 }
 
@@ -162,7 +140,7 @@ __device__ __forceinline__ void gc_y_store(float v, long idx, int col, const T* 
 
 // y epilogue of a wave's MFMA accumulator pair (D-fragment row ownership)
 template <typename T>
-__device__ __forceinline__ void gc_y_store_frag(const gc_f32x4* acc, int b, int n0,
+__device__ __forceinline__ void gc_y_store_frag(const f32x4* acc, int b, int n0,
                                                 int N, int Cout, GcLane l,
                                                 const T* bias, float* yacc, T* yout,
                                                 int first, int act) {
@@ -197,17 +175,17 @@ __device__ __forceinline__ void gc_u_pass(const char* dzt, const T* W, int kofs,
     using frag = typename Frag8<T>::type;
     const GcLane l;
     if (l.wv < (C >> 4)) {             // wave wv owns U cols [16wv, 16wv+16)
-      gc_f32x4 acc[2];
-      acc[0] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
-      acc[1] = gc_f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 acc[2];
+      acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int kk = 0; kk < (Cout >> 5); ++kk) {
         // W_j^T[co][c] = W[kofs + c][co] -> 8 consecutive co per lane: one load
         frag bfr =
             *(const frag*)&W[(kofs + 16 * l.wv + l.l16) * Cout + kk * 32 + l.lgrp * 8];
         frag a0 = *(const frag*)&dzt[lds_swz(l.l16, (kk * 32 + l.lgrp * 8) * 2)];
         frag a1 = *(const frag*)&dzt[lds_swz(16 + l.l16, (kk * 32 + l.lgrp * 8) * 2)];
-        acc[0] = gc_mfma(a0, bfr, acc[0]);
-        acc[1] = gc_mfma(a1, bfr, acc[1]);
+        acc[0] = mfma16x16x32(a0, bfr, acc[0]);
+        acc[1] = mfma16x16x32(a1, bfr, acc[1]);
       }
       #pragma unroll
       for (int m = 0; m < 2; ++m)

@@ -469,227 +469,7 @@ static int gate_chunks(int B, long work_per_b) {
   return (int)nch;
 }
 
-template <typename T>
-static void launch_gate_fwd(hipStream_t st, const T* g, const T* xs,
-                            const T* fcw, const T* fcb, const T* obs,
-                            float* z, float* u, float* s, unsigned* tickets,
-                            T* out, int B, int Tst, int N, int C, int nm) {
-  // z and tickets arrive zeroed (one fill); z doubles as the zsum atomic target
-  const dim3 gridA(gate_chunks(B, N), B);
-  hipLaunchKernelGGL(gate_fwd_reduce_kernel<T>, gridA, dim3(256), 0, st,
-                     g, xs, z, fcw, fcb, u, s, tickets, N, Tst);
-  const long total = (long)B * Tst * N * C;
-  const dim3 gridB((total + 255) / 256);
-  if (nm)
-    hipLaunchKernelGGL((gate_scale_kernel<T, true>), gridB, dim3(256), 0, st, obs,
-                       s, out, Tst, N, C, total);
-  else
-    hipLaunchKernelGGL((gate_scale_kernel<T, false>), gridB, dim3(256), 0, st, obs,
-                       s, out, Tst, N, C, total);
-}
-
-template <typename T>
-static void launch_gate_bwd(hipStream_t st, const T* dout, const T* obs,
-                            const T* fcw, const float* z, const float* u,
-                            const float* s, float* dz, float* dw_part,
-                            float* db_part, unsigned* tickets, float* dw_f,
-                            float* db_f, T* dw, T* db, T* dobs, T* dg,
-                            int B, int Tst, int N, int C, int nm) {
-  const long total = (long)B * Tst * N * C;
-  const float invN = 1.f / (float)N;
-  // dz and tickets arrive zeroed (one fill); dz doubles as the ds atomic target
-  const dim3 gridA(gate_chunks(B, (long)N * C), B);
-  const dim3 gridB((total + 255) / 256);
-  if (nm) {
-    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, true>), gridA, dim3(256), 0, st,
-                       dout, obs, dz, fcw, z, u, s, dw_part, db_part, tickets,
-                       dw_f, db_f, dw, db, N, C, Tst);
-    hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, true>), gridB, dim3(256), 0, st,
-                       dout, s, dz, dobs, dg, Tst, N, C, invN, total);
-  } else {
-    hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, false>), gridA, dim3(256), 0, st,
-                       dout, obs, dz, fcw, z, u, s, dw_part, db_part, tickets,
-                       dw_f, db_f, dw, db, N, C, Tst);
-    hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, false>), gridB, dim3(256), 0, st,
-                       dout, s, dz, dobs, dg, Tst, N, C, invN, total);
-  }
-}
-
 }  // namespace
-
-#define DISPATCH(fn, ...)                                        \
-  switch (dtype) {                                               \
-    case STM_F32: fn<float>(__VA_ARGS__); break;                 \
-    case STM_BF16: fn<__hip_bfloat16>(__VA_ARGS__); break;       \
-    case STM_F16: fn<__half>(__VA_ARGS__); break;                \
-  }
-
-extern "C" {
-
-void stmgcn_seqsum_permute(void* stream, int dtype, const void* obs, void* out,
-                           int B, int Tst, int N, int C) {
-  const long total = (long)B * N * Tst;
-  dim3 grid((total + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(seqsum_permute_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)obs, (float*)out, B, Tst, N, C); break;
-    case STM_BF16: hipLaunchKernelGGL(seqsum_permute_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)obs, (__hip_bfloat16*)out, B, Tst, N, C); break;
-    case STM_F16: hipLaunchKernelGGL(seqsum_permute_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)obs, (__half*)out, B, Tst, N, C); break;
-  }
-}
-
-void stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs,
-                               void* dobs, int B, int Tst, int N, int C) {
-  const long total = (long)B * Tst * N * C;
-  dim3 grid((total + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(seqsum_permute_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dxs, (float*)dobs, B, Tst, N, C); break;
-    case STM_BF16: hipLaunchKernelGGL(seqsum_permute_bwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dxs, (__hip_bfloat16*)dobs, B, Tst, N, C); break;
-    case STM_F16: hipLaunchKernelGGL(seqsum_permute_bwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dxs, (__half*)dobs, B, Tst, N, C); break;
-  }
-}
-
-
-// z (B*T floats) and tickets (B words) share one zero-filled allocation;
-// node_major: out is (B,N,T,C) instead of (B,T,N,C)
-void stmgcn_gate_fwd(void* stream, int dtype, const void* g, const void* xs,
-                     const void* fcw, const void* fcb, const void* obs,
-                     float* z, float* u, float* s, unsigned* tickets, void* out,
-                     int B, int Tst, int N, int C, int node_major) {
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case STM_F32:
-      launch_gate_fwd<float>(st, (const float*)g, (const float*)xs, (const float*)fcw, (const float*)fcb, (const float*)obs, z, u, s, tickets, (float*)out, B, Tst, N, C, node_major);
-      break;
-    case STM_BF16:
-      launch_gate_fwd<__hip_bfloat16>(st, (const __hip_bfloat16*)g, (const __hip_bfloat16*)xs, (const __hip_bfloat16*)fcw, (const __hip_bfloat16*)fcb, (const __hip_bfloat16*)obs, z, u, s, tickets, (__hip_bfloat16*)out, B, Tst, N, C, node_major);
-      break;
-    case STM_F16:
-      launch_gate_fwd<__half>(st, (const __half*)g, (const __half*)xs, (const __half*)fcw, (const __half*)fcb, (const __half*)obs, z, u, s, tickets, (__half*)out, B, Tst, N, C, node_major);
-      break;
-  }
-}
-
-// dz (B*T floats) and tickets (B + 1 words) share one zero-filled allocation;
-// dw_f/db_f: fp32 sums over the batch, dw/db the same in `dtype`; dobs may be
-// null (obs needs no gradient); node_major: dout is (B,N,T,C)
-void stmgcn_gate_bwd(void* stream, int dtype, const void* dout, const void* obs,
-                     const void* fcw, const float* z, const float* u,
-                     const float* s, float* dz, float* dw_part, float* db_part,
-                     unsigned* tickets, float* dw_f, float* db_f, void* dw,
-                     void* db, void* dobs, void* dg, int B, int Tst, int N, int C,
-                     int node_major) {
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case STM_F32:
-      launch_gate_bwd<float>(st, (const float*)dout, (const float*)obs, (const float*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (float*)dw, (float*)db, (float*)dobs, (float*)dg, B, Tst, N, C, node_major);
-      break;
-    case STM_BF16:
-      launch_gate_bwd<__hip_bfloat16>(st, (const __hip_bfloat16*)dout, (const __hip_bfloat16*)obs, (const __hip_bfloat16*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (__hip_bfloat16*)dw, (__hip_bfloat16*)db, (__hip_bfloat16*)dobs, (__hip_bfloat16*)dg, B, Tst, N, C, node_major);
-      break;
-    case STM_F16:
-      launch_gate_bwd<__half>(st, (const __half*)dout, (const __half*)obs, (const __half*)fcw, z, u, s, dz, dw_part, db_part, tickets, dw_f, db_f, (__half*)dw, (__half*)db, (__half*)dobs, (__half*)dg, B, Tst, N, C, node_major);
-      break;
-  }
-}
-
-void stmgcn_head_fwd(void* stream, int dtype, const void* f0, const void* f1,
-                     const void* f2, const void* w, const void* bias, void* y,
-                     void* fsum, int G, long BN) {
-  dim3 grid((BN * 64 + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(head_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)f0, (const float*)f1, (const float*)f2, (const float*)w, (const float*)bias, (float*)y, (float*)fsum, G, BN); break;
-    case STM_BF16: hipLaunchKernelGGL(head_fwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)f0, (const __hip_bfloat16*)f1, (const __hip_bfloat16*)f2, (const __hip_bfloat16*)w, (const __hip_bfloat16*)bias, (__hip_bfloat16*)y, (__hip_bfloat16*)fsum, G, BN); break;
-    case STM_F16: hipLaunchKernelGGL(head_fwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)f0, (const __half*)f1, (const __half*)f2, (const __half*)w, (const __half*)bias, (__half*)y, (__half*)fsum, G, BN); break;
-  }
-}
-
-void stmgcn_head_bwd(void* stream, int dtype, const void* dy, const void* w,
-                     void* dfeat, int G, long BN) {
-  const long total = BN * G;
-  dim3 grid((total + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(head_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)w, (float*)dfeat, G, total); break;
-    case STM_BF16: hipLaunchKernelGGL(head_bwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)w, (__hip_bfloat16*)dfeat, G, total); break;
-    case STM_F16: hipLaunchKernelGGL(head_bwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)w, (__half*)dfeat, G, total); break;
-  }
-}
-
-void stmgcn_head_wgrad(void* stream, int dtype, const void* dy,
-                       const void* fsum, float* dw, float* db, int G,
-                       long BN) {
-  long nblk = (BN + 255) / 256;   // fill the chip: 128+ blocks at bench size
-  if (nblk > 512) nblk = 512;
-  if (nblk < 1) nblk = 1;
-  dim3 grid((unsigned)nblk);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL((head_wgrad_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
-    case STM_BF16: hipLaunchKernelGGL((head_wgrad_kernel<__hip_bfloat16, false>), grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
-    case STM_F16: hipLaunchKernelGGL((head_wgrad_kernel<__half, false>), grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)fsum, dw, db, G, BN, nullptr, nullptr, nullptr); break;
-  }
-}
-
-// finishing form: dw_out (G,) / db_out (1,) in the dtype of dy
-void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy,
-                             const void* fsum, float* dw, float* db,
-                             unsigned* ticket, void* dw_out, void* db_out,
-                             int G, long BN) {
-  long nblk = (BN + 255) / 256;
-  if (nblk > 512) nblk = 512;
-  if (nblk < 1) nblk = 1;
-  dim3 grid((unsigned)nblk);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL((head_wgrad_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)fsum, dw, db, G, BN, ticket, (float*)dw_out, (float*)db_out); break;
-    case STM_BF16: hipLaunchKernelGGL((head_wgrad_kernel<__hip_bfloat16, true>), grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)fsum, dw, db, G, BN, ticket, (__hip_bfloat16*)dw_out, (__hip_bfloat16*)db_out); break;
-    case STM_F16: hipLaunchKernelGGL((head_wgrad_kernel<__half, true>), grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)fsum, dw, db, G, BN, ticket, (__half*)dw_out, (__half*)db_out); break;
-  }
-}
-
-void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,
-                     void* dz, long n) {
-  if (n <= 0) return;
-  const int vec = (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dz) & 15) == 0;
-  dim3 grid((unsigned)((n + 2047) / 2048));
-  switch (dtype) {
-    case STM_BF16: hipLaunchKernelGGL(relu_bwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)y, (__hip_bfloat16*)dz, n, vec); break;
-    case STM_F16: hipLaunchKernelGGL(relu_bwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)dy, (const __half*)y, (__half*)dz, n, vec); break;
-    default: printf("stmgcn_relu_bwd: unsupported dtype %d (bf16/f16 only)\n", dtype);
-  }
-}
-
-void stmgcn_mse_fwd(void* stream, int dtype, const void* pred, const void* tgt,
-                    float* loss, void* diff, long n) {
-  dim3 grid((n + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(mse_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pred, (const float*)tgt, loss, (float*)diff, n); break;
-    case STM_BF16: hipLaunchKernelGGL(mse_fwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)pred, (const __hip_bfloat16*)tgt, loss, (__hip_bfloat16*)diff, n); break;
-    case STM_F16: hipLaunchKernelGGL(mse_fwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)pred, (const __half*)tgt, loss, (__half*)diff, n); break;
-  }
-}
-
-void stmgcn_mse_bwd(void* stream, int dtype, const void* diff, const float* gscale,
-                    void* dpred, long n) {
-  dim3 grid((n + 255) / 256);
-  const float ton = 2.f / (float)n;
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(mse_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)diff, gscale, (float*)dpred, ton, n); break;
-    case STM_BF16: hipLaunchKernelGGL(mse_bwd_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, (const __hip_bfloat16*)diff, gscale, (__hip_bfloat16*)dpred, ton, n); break;
-    case STM_F16: hipLaunchKernelGGL(mse_bwd_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, (const __half*)diff, gscale, (__half*)dpred, ton, n); break;
-  }
-}
-
-void stmgcn_adam(void* stream, int dtype, float* master, void* param,
-                 const void* grad, float* m, float* v, float* hyper,
-                 long n) {
-  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper);
-  dim3 grid((n + 255) / 256);
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(adam_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, master, (float*)param, (const float*)grad, m, v, hyper, n); break;
-    case STM_BF16: hipLaunchKernelGGL(adam_kernel<__hip_bfloat16>, grid, dim3(256), 0, (hipStream_t)stream, master, (__hip_bfloat16*)param, (const __hip_bfloat16*)grad, m, v, hyper, n); break;
-    case STM_F16: hipLaunchKernelGGL(adam_kernel<__half>, grid, dim3(256), 0, (hipStream_t)stream, master, (__half*)param, (const __half*)grad, m, v, hyper, n); break;
-  }
-}
-
-}  // extern "C"
 
 // ---- K9b: multi-segment gradient gather into the flat Adam arena ----------
 // FusedAdam runs autograd with .grad = None (no per-param accumulate-add
@@ -714,11 +494,190 @@ __global__ void gather_grads_kernel(GatherSeg a, T* __restrict__ arena,
   for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < len; i += step)
     dst[i] = s ? s[i] : fromF<T>(0.f);
 }
+
+// one thread per element, 256 per workgroup
+inline dim3 grid1d(long total) { return dim3((unsigned)((total + 255) / 256)); }
 }  // namespace
 
-extern "C" void stmgcn_gather_grads(void* stream, int dtype, const void** srcs,
-                                    const long* ofs, const int* lens, int nseg,
-                                    void* arena) {
+// ---- entry points: T comes from the dtype code (stm_dispatch_dtype) --------
+extern "C" {
+
+void stmgcn_seqsum_permute(void* stream, int dtype, const void* obs, void* out,
+                           int B, int Tst, int N, int C) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(seqsum_permute_kernel<T>, grid1d((long)B * N * Tst),
+                       dim3(256), 0, (hipStream_t)stream, (const T*)obs, (T*)out,
+                       B, Tst, N, C);
+  });
+}
+
+void stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs,
+                               void* dobs, int B, int Tst, int N, int C) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(seqsum_permute_bwd_kernel<T>,
+                       grid1d((long)B * Tst * N * C), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)dxs, (T*)dobs, B, Tst, N, C);
+  });
+}
+
+// z (B*T floats) and tickets (B words) share one zero-filled allocation (z
+// doubles as the zsum atomic target); node_major: out is (B,N,T,C) instead of
+// (B,T,N,C)
+void stmgcn_gate_fwd(void* stream, int dtype, const void* g, const void* xs,
+                     const void* fcw, const void* fcb, const void* obs,
+                     float* z, float* u, float* s, unsigned* tickets, void* out,
+                     int B, int Tst, int N, int C, int node_major) {
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)B * Tst * N * C;
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gate_fwd_reduce_kernel<T>, dim3(gate_chunks(B, N), B),
+                       dim3(256), 0, st, (const T*)g, (const T*)xs, z,
+                       (const T*)fcw, (const T*)fcb, u, s, tickets, N, Tst);
+    stm_dispatch_bool(node_major != 0, [&](auto nm) {
+      hipLaunchKernelGGL((gate_scale_kernel<T, decltype(nm)::value>),
+                         grid1d(total), dim3(256), 0, st, (const T*)obs, s,
+                         (T*)out, Tst, N, C, total);
+    });
+  });
+}
+
+// dz (B*T floats) and tickets (B + 1 words) share one zero-filled allocation
+// (dz doubles as the ds atomic target); dw_f/db_f: fp32 sums over the batch,
+// dw/db the same in `dtype`; dobs may be null (obs needs no gradient);
+// node_major: dout is (B,N,T,C)
+void stmgcn_gate_bwd(void* stream, int dtype, const void* dout, const void* obs,
+                     const void* fcw, const float* z, const float* u,
+                     const float* s, float* dz, float* dw_part, float* db_part,
+                     unsigned* tickets, float* dw_f, float* db_f, void* dw,
+                     void* db, void* dobs, void* dg, int B, int Tst, int N, int C,
+                     int node_major) {
+  hipStream_t st = (hipStream_t)stream;
+  const long total = (long)B * Tst * N * C;
+  const float invN = 1.f / (float)N;
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    stm_dispatch_bool(node_major != 0, [&](auto nm) {
+      constexpr bool NM = decltype(nm)::value;
+      hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, NM>),
+                         dim3(gate_chunks(B, (long)N * C), B), dim3(256), 0, st,
+                         (const T*)dout, (const T*)obs, dz, (const T*)fcw, z, u,
+                         s, dw_part, db_part, tickets, dw_f, db_f, (T*)dw,
+                         (T*)db, N, C, Tst);
+      hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, NM>), grid1d(total),
+                         dim3(256), 0, st, (const T*)dout, s, dz, (T*)dobs,
+                         (T*)dg, Tst, N, C, invN, total);
+    });
+  });
+}
+
+void stmgcn_head_fwd(void* stream, int dtype, const void* f0, const void* f1,
+                     const void* f2, const void* w, const void* bias, void* y,
+                     void* fsum, int G, long BN) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(head_fwd_kernel<T>, grid1d(BN * 64), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)f0, (const T*)f1,
+                       (const T*)f2, (const T*)w, (const T*)bias, (T*)y,
+                       (T*)fsum, G, BN);
+  });
+}
+
+void stmgcn_head_bwd(void* stream, int dtype, const void* dy, const void* w,
+                     void* dfeat, int G, long BN) {
+  const long total = BN * G;
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(head_bwd_kernel<T>, grid1d(total), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)dy, (const T*)w,
+                       (T*)dfeat, G, total);
+  });
+}
+
+// ticket == null: the accumulate-only form (fp32 sums left in dw / db);
+// otherwise the finishing form, dw_out (G,) / db_out (1,) in the dtype of dy
+static void head_wgrad_launch(void* stream, int dtype, const void* dy,
+                              const void* fsum, float* dw, float* db,
+                              unsigned* ticket, void* dw_out, void* db_out,
+                              int G, long BN) {
+  long nblk = (BN + 255) / 256;   // fill the chip: 128+ blocks at bench size
+  if (nblk > 512) nblk = 512;
+  if (nblk < 1) nblk = 1;
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    stm_dispatch_bool(ticket != nullptr, [&](auto fin) {
+      hipLaunchKernelGGL((head_wgrad_kernel<T, decltype(fin)::value>),
+                         dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
+                         (const T*)dy, (const T*)fsum, dw, db, G, BN, ticket,
+                         (T*)dw_out, (T*)db_out);
+    });
+  });
+}
+
+void stmgcn_head_wgrad(void* stream, int dtype, const void* dy,
+                       const void* fsum, float* dw, float* db, int G,
+                       long BN) {
+  head_wgrad_launch(stream, dtype, dy, fsum, dw, db, nullptr, nullptr, nullptr,
+                    G, BN);
+}
+
+void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy,
+                             const void* fsum, float* dw, float* db,
+                             unsigned* ticket, void* dw_out, void* db_out,
+                             int G, long BN) {
+  head_wgrad_launch(stream, dtype, dy, fsum, dw, db, ticket, dw_out, db_out, G,
+                    BN);
+}
+
+void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,
+                     void* dz, long n) {
+  if (n <= 0) return;
+  const int vec = (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dz) & 15) == 0;
+  stm_dispatch_lowp("stmgcn_relu_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3((unsigned)((n + 2047) / 2048)),
+                       dim3(256), 0, (hipStream_t)stream, (const T*)dy,
+                       (const T*)y, (T*)dz, n, vec);
+  });
+}
+
+void stmgcn_mse_fwd(void* stream, int dtype, const void* pred, const void* tgt,
+                    float* loss, void* diff, long n) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(mse_fwd_kernel<T>, grid1d(n), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)pred, (const T*)tgt, loss,
+                       (T*)diff, n);
+  });
+}
+
+void stmgcn_mse_bwd(void* stream, int dtype, const void* diff, const float* gscale,
+                    void* dpred, long n) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(mse_bwd_kernel<T>, grid1d(n), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)diff, gscale, (T*)dpred,
+                       2.f / (float)n, n);
+  });
+}
+
+void stmgcn_adam(void* stream, int dtype, float* master, void* param,
+                 const void* grad, float* m, float* v, float* hyper,
+                 long n) {
+  hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper);
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(adam_kernel<T>, grid1d(n), dim3(256), 0,
+                       (hipStream_t)stream, master, (T*)param, (const T*)grad, m,
+                       v, hyper, n);
+  });
+}
+
+void stmgcn_gather_grads(void* stream, int dtype, const void** srcs,
+                         const long* ofs, const int* lens, int nseg,
+                         void* arena) {
   GatherSeg a;
   int maxlen = 1;
   for (int i = 0; i < nseg && i < 64; ++i) {
@@ -726,11 +685,11 @@ extern "C" void stmgcn_gather_grads(void* stream, int dtype, const void** srcs,
     if (lens[i] > maxlen) maxlen = lens[i];
   }
   const int chunks = min(8, (maxlen + 2047) / 2048);
-  const dim3 grid(nseg, chunks), blk(256);
-  hipStream_t st = (hipStream_t)stream;
-  switch (dtype) {
-    case STM_F32: hipLaunchKernelGGL(gather_grads_kernel<float>, grid, blk, 0, st, a, (float*)arena, nseg); break;
-    case STM_BF16: hipLaunchKernelGGL(gather_grads_kernel<__hip_bfloat16>, grid, blk, 0, st, a, (__hip_bfloat16*)arena, nseg); break;
-    case STM_F16: hipLaunchKernelGGL(gather_grads_kernel<__half>, grid, blk, 0, st, a, (__half*)arena, nseg); break;
-  }
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gather_grads_kernel<T>, dim3(nseg, chunks), dim3(256), 0,
+                       (hipStream_t)stream, a, (T*)arena, nseg);
+  });
 }
+
+}  // extern "C"

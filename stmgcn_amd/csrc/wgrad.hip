@@ -23,81 +23,31 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 namespace {
 
-template <typename T> struct WFrag8;
-template <> struct WFrag8<__hip_bfloat16> { using type = bf16x8; using elem = __bf16; };
-template <> struct WFrag8<__half> { using type = f16x8; using elem = _Float16; };
-
-__device__ __forceinline__ f32x4 wmfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 wmfma(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// Transposed-tile LDS addressing: column g (output dim), row byte offset off.
-// 32-row tiles (64 B/col): XOR displaces the 16 B fragment window so the MFMA
-// reads (16 consecutive g, 16 B each) hit 64 distinct banks; 64-row tiles
-// (128 B/col) use row parity for the 32-bank half + ((g>>1)&7) window perm.
+// Transposed-tile LDS addressing: column g (output dim) holds RB bytes of
+// reduction rows (RB = 64: 32-row tiles, RB = 128: 64-row K-steps), off is the
+// byte offset inside the column. The 256 / RB columns that share one 256 B
+// line of the 64 banks keep their 16 B windows and successive lines XOR-rotate
+// them, so an MFMA fragment read (16 consecutive g, 16 B each) hits 64
+// distinct banks.
+template <int RB>
 __device__ __forceinline__ int tswz(int g, int off) {
-  return g * 64 + (off ^ ((((unsigned)g >> 2) & 3) << 4));
+  return g * RB + (off ^ ((((unsigned)g / (256 / RB)) & (RB / 16 - 1)) << 4));
 }
-__device__ __forceinline__ int tswz64(int g, int off) {
-  return g * 128 + (off ^ ((((unsigned)g >> 1) & 7) << 4));
-}
-template <typename T>
-__device__ __forceinline__ typename WFrag8<T>::type frag_from64(
+
+// A-fragment (or B-fragment) read from a transposed LDS tile: output index g,
+// reduction rows k = koff_bytes / 2 .. +8 -> the 16 B at tswz(g, koff_bytes).
+template <typename T, int RB>
+__device__ __forceinline__ typename Frag8<T>::type frag_from(
     const char* lds_tile, int g, int koff_bytes) {
-  return *(const typename WFrag8<T>::type*)&lds_tile[tswz64(g, koff_bytes)];
-}
-
-// Stage one 32-row tile of src (rows-major, ld elems) transposed into LDS
-// tile [ncols][32] (64B/col). Unit u -> (pair pr = u & 15, col-block cb =
-// u >> 4, 8 cols each); zero-fills guarded rows/cols. Each thread covers
-// units {tid, tid+256, ...} so a caller tracking column sums per unit slot
-// keeps a fixed col-block per slot.
-template <typename T, int NUNITS>
-__device__ __forceinline__ void stage_tileT(
-    char* lds_tile, const T* __restrict__ src, long ld, long r0, long rmax,
-    int ncols, float* colsum /* per-thread [NUNITS/256][8] or null */) {
-  using frag = typename WFrag8<T>::type;
-  for (int u = threadIdx.x, slot = 0; u < NUNITS; u += 256, ++slot) {
-    const int pr = u & 15, cb = u >> 4;
-    const long r = r0 + pr * 2;
-    frag v0 = {}, v1 = {};
-    if (cb * 8 < ncols) {
-      if (r < rmax) v0 = *(const frag*)&src[r * ld + cb * 8];
-      if (r + 1 < rmax) v1 = *(const frag*)&src[(r + 1) * ld + cb * 8];
-    }
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int g = cb * 8 + j;
-      union { T t2[2]; int i; } pk;
-      pk.t2[0] = ((const T*)&v0)[j];
-      pk.t2[1] = ((const T*)&v1)[j];
-      *(int*)&lds_tile[tswz(g, pr * 4)] = pk.i;
-      if (colsum) colsum[slot * 8 + j] += toF<T>(pk.t2[0]) + toF<T>(pk.t2[1]);
-    }
-  }
-}
-
-// A-fragment (or B-fragment) read from a transposed LDS tile: output index
-// g = g0 + l16, reduction k = lgrp*8..+8 -> 16B at tswz(g, lgrp*16).
-template <typename T>
-__device__ __forceinline__ typename WFrag8<T>::type frag_from(
-    const char* lds_tile, int g, int lgrp) {
-  return *(const typename WFrag8<T>::type*)&lds_tile[tswz(g, lgrp * 16)];
+  return *(const typename Frag8<T>::type*)&lds_tile[tswz<RB>(g, koff_bytes)];
 }
 
 }  // namespace
 
 // ===========================================================================
-// Fused multi-layer LSTM weight gradients: one launch, grid (nchunks, L, 256/GT).
+// Fused multi-layer LSTM weight gradients: one launch, grid (nchunks, L).
 //   dwih[l] += dA_l^T @ (l == 0 ? x : hseq[l-1])      (4H, cin_l<=64)
 //   dwhh[l] += dA_l^T @ hseq[l] shifted one step back (4H, H)
 //   db[l]   += colsum(dA_l)                           (4H,)
@@ -116,16 +66,14 @@ __device__ __forceinline__ typename WFrag8<T>::type frag_from(
 // db is the fp32 sum of each A-fragment's 8 values, reduced across lgrp by
 // two shuffles at the end.
 //
-// Every wave owns 32 gate rows (2 m-tiles); GT = gate rows per workgroup:
-// GT = 256 (512 threads) consumes whole dA rows per workgroup so hp/hx are
-// staged ONCE; GT = 128 (256 threads, grid.z = 2) re-reads them per slice.
-// The generic instantiation serves every layer in ONE launch (cin1 != 0:
-// layer 0 reads the scalar input x and only column 0 of its dw_ih is live).
-// The L0CIN1 instantiation covers ONLY layer 0 of that scalar-input model
-// with acc_ih collapsed to one n-tile, for the split two-launch variant
-// (STMGCN_WGRAD_SPLIT_L0=1). layer = blockIdx.y + lbase. Chunks are whole
-// tiles (tpc per workgroup); an odd tile count leaves the second half of the
-// last K-step zero.
+// Every wave owns 32 gate rows (2 m-tiles), so the 8 waves of a 512-thread
+// workgroup consume whole dA rows and hp/hx are staged once. One launch
+// serves every layer, layer = blockIdx.y (cin1 != 0: layer 0 reads the scalar
+// input x and only column 0 of its dw_ih is live). A 256-thread gate-split
+// form and a separate single-column launch for that layer 0 both measured
+// slower (profiles/r03_da_stream_layout.md). Chunks are whole tiles (tpc per
+// workgroup); an odd tile count leaves the second half of the last K-step
+// zero.
 //
 // FIN (the finishing form): after its atomics every workgroup arrives at its
 // layer's ticket (stm_last_arriver, common.h); the last one of a layer reads
@@ -147,26 +95,24 @@ __host__ __device__ inline long lstm_grads_layer_off(int l, int GH, int cin) {
   return l == 0 ? 0 : (long)GH * (cin + 64 + 2) + (long)(l - 1) * GH * (64 + 64 + 2);
 }
 
-template <typename T, bool L0CIN1, int GT, bool FIN>
-__global__ void __launch_bounds__(GT * 2, 1)
+template <typename T, bool FIN>
+__global__ void __launch_bounds__(512, 1)
 lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
                   const T* __restrict__ x, float* __restrict__ dwih,
                   float* __restrict__ dwhh, float* __restrict__ db,
-                  long R, long S_pad, int S, int Tst, int L, int lbase,
-                  int cin1, long tpc, LstmFin<T> fin) {
-  using frag = typename WFrag8<T>::type;
-  constexpr int NTHR = GT * 2;      // one wave per 32 gate rows
+                  long R, long S_pad, int S, int Tst, int L, int cin1,
+                  long tpc, LstmFin<T> fin) {
+  using frag = typename Frag8<T>::type;
+  constexpr int NTHR = 512;         // one wave per 32 of the 256 gate rows
   constexpr int MTG = 2;            // gate m-tiles per wave
   constexpr int KT = 64;            // K-step rows = two dA tiles
-  constexpr int UPT = 512 / NTHR;   // hp/hx staging units per thread per K-step
   constexpr int HT = 64 * 2 * KT;   // one transposed [64][KT] tile, bytes
-  static_assert(GT == 128 || GT == 256, "staging map covers 256/512 threads");
   extern __shared__ char lds[];     // 2 x (hpT | hxT)
 
-  const int layer = blockIdx.y + lbase;
+  const int layer = blockIdx.y;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l16 = lane & 15, lgrp = lane >> 4;
-  const int gw = blockIdx.z * GT + wv * 32;   // this wave's first gate row
+  const int gw = wv * 32;                     // this wave's first gate row
   const long ntile = R / SEQ_TILE;
   const long tb0 = (long)blockIdx.x * tpc;
   const long tb1 = (tb0 + tpc < ntile) ? tb0 + tpc : ntile;
@@ -179,73 +125,67 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   const T* dA_l = dA + (long)layer * R * STM_DA_GATES;
   const T* hp_l = hseq + (long)layer * R * 64;       // index r - S_pad
   const T* hx_l = (layer > 0) ? hseq + (long)(layer - 1) * R * 64 : nullptr;
-  const bool l0 = L0CIN1 || (layer == 0);
-  const bool x1 = L0CIN1 || (cin1 && layer == 0);   // scalar layer-0 input
-  constexpr int IHNT = L0CIN1 ? 1 : 4;   // dw_ih n-tiles
+  const bool l0 = layer == 0;
+  const bool x1 = cin1 && l0;   // scalar layer-0 input
 
-  f32x4 acc_hh[MTG][4], acc_ih[MTG][IHNT];
+  f32x4 acc_hh[MTG][4], acc_ih[MTG][4];
   float dbp[MTG];
   #pragma unroll
   for (int mt = 0; mt < MTG; ++mt) {
     #pragma unroll
     for (int nt = 0; nt < 4; ++nt) acc_hh[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     #pragma unroll
-    for (int nt = 0; nt < IHNT; ++nt) acc_ih[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < 4; ++nt) acc_ih[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
     dbp[mt] = 0.f;
   }
 
-  // hp/hx staging unit (512 per K-step: 2 operands x 32 row pairs x 8 column
-  // blocks): row pair p sits at k' = 2p, 2p+1 of K-half p >> 4, i.e. tile
-  // rows rho(2(p&15)) and the next one (rho keeps even/odd k' pairs adjacent).
-  // 8 consecutive lanes take the 8 column blocks of one row: 128 B coalesced.
+  // hp/hx staging: one unit per thread per K-step (2 operands x 32 row pairs
+  // x 8 column blocks): row pair p sits at k' = 2p, 2p+1 of K-half p >> 4,
+  // i.e. tile rows rho(2(p&15)) and the next one (rho keeps even/odd k' pairs
+  // adjacent). 8 consecutive lanes take the 8 column blocks of one row: 128 B
+  // coalesced. Threads 0..255 stage hp, 256..511 stage hx.
   const int scb = threadIdx.x & 7, sp = (threadIdx.x >> 3) & 31;
   const int skh = sp >> 4, srow = stm_da_rho(2 * (sp & 15));
-  auto unit_op = [&](int u) { return (int)((threadIdx.x + u * NTHR) >> 8); };
+  const int sop = threadIdx.x >> 8;
 
-  auto load_h = [&](long tb, frag v[UPT][2]) {
+  auto load_h = [&](long tb, frag v[2]) {
     const frag fz = {};
     const long tile = tb + skh;
     const long r = tile * SEQ_TILE + srow;     // rows r, r + 1 (same tile)
-    #pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      v[u][0] = fz; v[u][1] = fz;
-      if (tile >= tb1) continue;
-      if (unit_op(u) == 0) {
-        // h_{t-1}: hseq[l] offset -S_pad rows, zero for t==0 (the guard must
-        // gate the LOAD — for layer 0, r - S_pad points before the allocation)
-        if (tile >= tp0) {
-          v[u][0] = *(const frag*)&hp_l[(r - S_pad) * 64 + scb * 8];
-          v[u][1] = *(const frag*)&hp_l[(r + 1 - S_pad) * 64 + scb * 8];
+    v[0] = fz; v[1] = fz;
+    if (tile >= tb1) return;
+    if (sop == 0) {
+      // h_{t-1}: hseq[l] offset -S_pad rows, zero for t==0 (the guard must
+      // gate the LOAD — for layer 0, r - S_pad points before the allocation)
+      if (tile >= tp0) {
+        v[0] = *(const frag*)&hp_l[(r - S_pad) * 64 + scb * 8];
+        v[1] = *(const frag*)&hp_l[(r + 1 - S_pad) * 64 + scb * 8];
+      }
+    } else if (!l0) {
+      v[0] = *(const frag*)&hx_l[r * 64 + scb * 8];
+      v[1] = *(const frag*)&hx_l[(r + 1) * 64 + scb * 8];
+    } else {
+      const long s_ = r % S_pad, t_ = r / S_pad;   // pad rows (s >= S) stay 0
+      if (x1) {
+        if (scb == 0) {
+          if (s_ < S) ((T*)&v[0])[0] = x[s_ * Tst + t_];
+          if (s_ + 1 < S) ((T*)&v[1])[0] = x[(s_ + 1) * Tst + t_];
         }
-      } else if (!l0) {
-        v[u][0] = *(const frag*)&hx_l[r * 64 + scb * 8];
-        v[u][1] = *(const frag*)&hx_l[(r + 1) * 64 + scb * 8];
       } else {
-        const long s_ = r % S_pad, t_ = r / S_pad;   // pad rows (s >= S) stay 0
-        if (x1) {
-          if (scb == 0) {
-            if (s_ < S) ((T*)&v[u][0])[0] = x[s_ * Tst + t_];
-            if (s_ + 1 < S) ((T*)&v[u][1])[0] = x[(s_ + 1) * Tst + t_];
-          }
-        } else {
-          if (s_ < S) v[u][0] = *(const frag*)&x[(s_ * Tst + t_) * 64 + scb * 8];
-          if (s_ + 1 < S)
-            v[u][1] = *(const frag*)&x[((s_ + 1) * Tst + t_) * 64 + scb * 8];
-        }
+        if (s_ < S) v[0] = *(const frag*)&x[(s_ * Tst + t_) * 64 + scb * 8];
+        if (s_ + 1 < S)
+          v[1] = *(const frag*)&x[((s_ + 1) * Tst + t_) * 64 + scb * 8];
       }
     }
   };
-  auto commit_h = [&](char* buf, const frag v[UPT][2]) {
+  auto commit_h = [&](char* buf, const frag v[2]) {
+    char* tileT = buf + sop * HT;
     #pragma unroll
-    for (int u = 0; u < UPT; ++u) {
-      char* tileT = buf + unit_op(u) * HT;
-      #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        union { T t2[2]; int i; } pk;
-        pk.t2[0] = ((const T*)&v[u][0])[j];
-        pk.t2[1] = ((const T*)&v[u][1])[j];
-        *(int*)&tileT[tswz64(scb * 8 + j, sp * 4)] = pk.i;
-      }
+    for (int j = 0; j < 8; ++j) {
+      union { T t2[2]; int i; } pk;
+      pk.t2[0] = ((const T*)&v[0])[j];
+      pk.t2[1] = ((const T*)&v[1])[j];
+      *(int*)&tileT[tswz<2 * KT>(scb * 8 + j, sp * 4)] = pk.i;
     }
   };
   // dA A-fragments of one K-step: [K-half = tile][m-tile]
@@ -268,7 +208,7 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   // two sets alternate by name (loop unrolled by 2): no register copies, so
   // no wait on a load that was only just issued. Past the chunk end the
   // loads issue nothing and leave zeros.
-  auto kstep = [&](long tb, char* buf, frag vs[UPT][2], frag a[2][MTG]) {
+  auto kstep = [&](long tb, char* buf, frag vs[2], frag a[2][MTG]) {
     char* hpT = buf;
     char* hxT = buf + HT;
     commit_h(buf, vs);
@@ -277,20 +217,20 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
     #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
       const int koff = kh * KT + lgrp * 16;   // byte offset of the K half
-      frag bh[4], bx[IHNT];
+      frag bh[4], bx[4];
       #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) bh[nt] = frag_from64<T>(hpT, nt * 16 + l16, koff);
+      for (int nt = 0; nt < 4; ++nt) bh[nt] = frag_from<T, 2 * KT>(hpT, nt * 16 + l16, koff);
       #pragma unroll
-      for (int nt = 0; nt < IHNT; ++nt) bx[nt] = frag_from64<T>(hxT, nt * 16 + l16, koff);
+      for (int nt = 0; nt < 4; ++nt) bx[nt] = frag_from<T, 2 * KT>(hxT, nt * 16 + l16, koff);
       #pragma unroll
       for (int mt = 0; mt < MTG; ++mt) {
         const frag af = a[kh][mt];
         #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
-          acc_hh[mt][nt] = wmfma(af, bh[nt], acc_hh[mt][nt]);
+          acc_hh[mt][nt] = mfma16x16x32(af, bh[nt], acc_hh[mt][nt]);
         #pragma unroll
-        for (int nt = 0; nt < IHNT; ++nt)
-          acc_ih[mt][nt] = wmfma(af, bx[nt], acc_ih[mt][nt]);
+        for (int nt = 0; nt < 4; ++nt)
+          acc_ih[mt][nt] = mfma16x16x32(af, bx[nt], acc_ih[mt][nt]);
         float sa = 0.f;
         #pragma unroll
         for (int j = 0; j < 8; ++j) sa += (float)af[j];
@@ -300,7 +240,7 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
     load_a(tb + 4, a);
   };
 
-  frag vs0[UPT][2], vs1[UPT][2], a0[2][MTG], a1[2][MTG];
+  frag vs0[2], vs1[2], a0[2][MTG], a1[2][MTG];
   load_h(tb0, vs0);
   load_a(tb0, a0);
   load_h(tb0 + 2, vs1);
@@ -323,8 +263,8 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
         const int m = gw + mt * 16 + lgrp * 4 + rr;
         const int n = nt * 16 + l16;
         unsafeAtomicAdd(&whh[m * 64 + n], acc_hh[mt][nt][rr]);
-        if (nt < IHNT && (!x1 || n == 0))   // scalar input: one live column
-          unsafeAtomicAdd(&wih[m * 64 + n], acc_ih[mt][nt < IHNT ? nt : 0][rr]);
+        if (!x1 || n == 0)   // scalar input: one live column
+          unsafeAtomicAdd(&wih[m * 64 + n], acc_ih[mt][nt][rr]);
       }
     // db: lane (l16, lgrp) holds the k' = 8*lgrp..+8 partial of gate l16
     float v = dbp[mt];
@@ -334,8 +274,7 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   }
 
   if constexpr (FIN) {
-    if (!stm_last_arriver(&fin.tickets[layer], gridDim.x * gridDim.z, (int*)lds))
-      return;
+    if (!stm_last_arriver(&fin.tickets[layer], gridDim.x, (int*)lds)) return;
     // packed gate row m -> output row (or -1: a zero GRU slot)
     const int GH = fin.gru ? 192 : 256;
     const int cin_l = l0 ? fin.cin : 64;
@@ -352,23 +291,20 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
     // sums as far as the compiler knows, so a load-store-load loop would pay
     // one memory round trip per iteration on this serial tail): float4 i of a
     // (256, 64) matrix is row i >> 4, columns 4 * (i & 15).
+    // Threads 0..255 also carry one gate row's bias sum (and, for the scalar
+    // input, its single dw_ih column).
     constexpr int IT = 256 * 16 / NTHR;   // float4 per thread per matrix
-    constexpr int BT = 256 / NTHR ? 256 / NTHR : 1;
     const bool dense = cin_l == 64;
+    const int mb = threadIdx.x;
     float4 vh[IT], vi[IT];
-    float vb[BT], vc[BT];
     #pragma unroll
     for (int k = 0; k < IT; ++k) {
       const int i = threadIdx.x + k * NTHR;
       vh[k] = *(const float4*)&whh[i * 4];
       vi[k] = dense ? *(const float4*)&wih[i * 4] : float4{0.f, 0.f, 0.f, 0.f};
     }
-    #pragma unroll
-    for (int k = 0; k < BT; ++k) {
-      const int m = threadIdx.x + k * NTHR;
-      vb[k] = m < 256 ? dbl[m] : 0.f;
-      vc[k] = (!dense && m < 256) ? wih[m * 64] : 0.f;
-    }
+    const float vb = mb < 256 ? dbl[mb] : 0.f;
+    const float vc = (!dense && mb < 256) ? wih[mb * 64] : 0.f;
     #pragma unroll
     for (int k = 0; k < IT; ++k) {
       const int i = threadIdx.x + k * NTHR;
@@ -379,35 +315,24 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
       if (dense && ri >= 0)
         stm_store4<T>(&o_ih[ri * 64 + n4], vi[k].x, vi[k].y, vi[k].z, vi[k].w);
     }
-    #pragma unroll
-    for (int k = 0; k < BT; ++k) {
-      const int m = threadIdx.x + k * NTHR;
-      if (m >= 256) continue;
-      const int ri = row_ih(m), rh = row_hh(m);
-      if (ri >= 0) o_bi[ri] = fromF<T>(vb[k]);
-      if (rh >= 0) o_bh[rh] = fromF<T>(vb[k]);
-      if (!dense && ri >= 0) o_ih[ri] = fromF<T>(vc[k]);
-    }
+    if (mb >= 256) return;
+    const int ri = row_ih(mb), rh = row_hh(mb);
+    if (ri >= 0) o_bi[ri] = fromF<T>(vb);
+    if (rh >= 0) o_bh[rh] = fromF<T>(vb);
+    if (!dense && ri >= 0) o_ih[ri] = fromF<T>(vc);
   }
 }
 
 // tickets/out == null: the accumulate-only form (fp32 sums left in place)
-static void lstm_wgrad_launch(void* stream_v, int dtype, const void* dA,
+static void lstm_wgrad_launch(void* stream, int dtype, const void* dA,
                               const void* hseq, const void* x, float* dwih,
                               float* dwhh, float* db, long R, long S_pad,
                               int S, int Tst, int L, int cin,
                               unsigned* tickets, void* out, int gru) {
   static long env_chunks = -1;   // STMGCN_WGRAD_CHUNKS: perf experiments
-  static int env_gt = -1;        // STMGCN_WGRAD_GT=128: gate-split variant
-  static int env_split = 0;      // STMGCN_WGRAD_SPLIT_L0=1: own launch for
-                                 // the scalar-input layer 0
   if (env_chunks < 0) {
     const char* e = getenv("STMGCN_WGRAD_CHUNKS");
     env_chunks = e ? atol(e) : 0;
-    const char* g = getenv("STMGCN_WGRAD_GT");
-    env_gt = (g && atoi(g) == 128) ? 128 : 256;
-    const char* sp = getenv("STMGCN_WGRAD_SPLIT_L0");
-    env_split = sp ? atoi(sp) : 0;
   }
   if (R <= 0 || R % SEQ_TILE != 0) {
     printf("stmgcn_lstm_wgrad: R=%ld is not a whole number of dA tiles\n", R);
@@ -422,42 +347,17 @@ static void lstm_wgrad_launch(void* stream_v, int dtype, const void* dA,
   const long tpc = (ntile + nchunks - 1) / nchunks;   // tiles per workgroup
   nchunks = (ntile + tpc - 1) / tpc;
   const size_t lds = 2 * 2 * 8192;   // double-buffered hpT | hxT, 64-row steps
-  hipStream_t stream = (hipStream_t)stream_v;
-  auto launch = [&](auto tptr, auto gtc, auto finc) {
-    using TT = std::remove_pointer_t<decltype(tptr)>;
-    constexpr int GT = decltype(gtc)::value;   // gate rows per workgroup
-    constexpr bool FIN = decltype(finc)::value;
-    const dim3 blk(GT * 2);
-    const LstmFin<TT> fin{tickets, (TT*)out, gru, cin};
-    if (cin == 1 && env_split) {
-      // layer 0 (single ih column) and layers >= 1 as separate instantiations
-      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, true, GT, FIN>),
-                         dim3((unsigned)nchunks, 1, 256 / GT), blk, lds, stream,
-                         (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, 1, tpc, fin);
-      if (L > 1)
-        hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT, FIN>),
-                           dim3((unsigned)nchunks, L - 1, 256 / GT), blk, lds,
-                           stream, (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                           dwih, dwhh, db, R, S_pad, S, Tst, L, 1, 0, tpc, fin);
-    } else {
-      hipLaunchKernelGGL((lstm_wgrad_kernel<TT, false, GT, FIN>),
-                         dim3((unsigned)nchunks, L, 256 / GT), blk, lds, stream,
-                         (const TT*)dA, (const TT*)hseq, (const TT*)x,
-                         dwih, dwhh, db, R, S_pad, S, Tst, L, 0, cin == 1 ? 1 : 0,
-                         tpc, fin);
-    }
-  };
-  auto by_gt = [&](auto tptr, auto finc) {
-    if (env_gt == 128) launch(tptr, std::integral_constant<int, 128>{}, finc);
-    else launch(tptr, std::integral_constant<int, 256>{}, finc);
-  };
-  auto by_fin = [&](auto tptr) {
-    if (out != nullptr) by_gt(tptr, std::true_type{});
-    else by_gt(tptr, std::false_type{});
-  };
-  if (dtype == STM_BF16) by_fin((__hip_bfloat16*)nullptr);
-  else if (dtype == STM_F16) by_fin((__half*)nullptr);
+  stm_dispatch_lowp("stmgcn_lstm_wgrad", dtype, [&](auto t) {
+    using T = decltype(t);
+    const LstmFin<T> fin{tickets, (T*)out, gru, cin};
+    stm_dispatch_bool(out != nullptr, [&](auto finc) {
+      hipLaunchKernelGGL((lstm_wgrad_kernel<T, decltype(finc)::value>),
+                         dim3((unsigned)nchunks, L), dim3(512), lds,
+                         (hipStream_t)stream, (const T*)dA, (const T*)hseq,
+                         (const T*)x, dwih, dwhh, db, R, S_pad, S, Tst, L,
+                         cin == 1 ? 1 : 0, tpc, fin);
+    });
+  });
 }
 
 extern "C" void stmgcn_lstm_wgrad(void* stream, int dtype, const void* dA,
@@ -510,7 +410,7 @@ __global__ void __launch_bounds__(256, 1)
 atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
                  float* __restrict__ C, float* __restrict__ db,
                  long rows, int M, int N, AtbFin<T> fin) {
-  using frag = typename WFrag8<T>::type;
+  using frag = typename Frag8<T>::type;
   extern __shared__ char lds[];
   char* AT = lds;                  // [256][32] -> 16 KiB
   char* BT = lds + 16384;         // [64][32]  ->  4 KiB
@@ -574,7 +474,7 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
         union { T t2[2]; int i; } pk;
         pk.t2[0] = ((const T*)&va[u][0])[j];
         pk.t2[1] = ((const T*)&va[u][1])[j];
-        *(int*)&AT[tswz(cb * 8 + j, pr * 4)] = pk.i;
+        *(int*)&AT[tswz<64>(cb * 8 + j, pr * 4)] = pk.i;
       }
     }
     if (threadIdx.x < 128) {
@@ -583,7 +483,7 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
         union { T t2[2]; int i; } pk;
         pk.t2[0] = ((const T*)&vb[0])[j];
         pk.t2[1] = ((const T*)&vb[1])[j];
-        *(int*)&BT[tswz(cbb * 8 + j, pr * 4)] = pk.i;
+        *(int*)&BT[tswz<64>(cbb * 8 + j, pr * 4)] = pk.i;
         if (db) dbp[j] += toF<T>(pk.t2[0]) + toF<T>(pk.t2[1]);
       }
     }
@@ -598,9 +498,10 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
     if (more) load_tiles(kt + 32, na, nb);
     for (int i = 0; i < mt_mine; ++i) {
       const int mt = wv + i * 4;
-      const frag a = frag_from<T>(AT, mt * 16 + l16, lgrp);
+      const frag a = frag_from<T, 64>(AT, mt * 16 + l16, lgrp * 16);
       for (int nt = 0; nt < ntiles; ++nt)
-        acc[i][nt] = wmfma(a, frag_from<T>(BT, nt * 16 + l16, lgrp), acc[i][nt]);
+        acc[i][nt] = mfma16x16x32(a, frag_from<T, 64>(BT, nt * 16 + l16, lgrp * 16),
+                                  acc[i][nt]);
     }
     __syncthreads();
     if (more) {
@@ -657,7 +558,7 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
 }
 
 // fin_ticket == null: the accumulate-into form (fp32 sums left in C / db)
-static void atb_wgrad_launch(void* stream_v, int dtype, const void** As,
+static void atb_wgrad_launch(void* stream, int dtype, const void** As,
                              int nsrc, int CA, const void* B, float* C,
                              float* db, long rows, int N, unsigned* fin_ticket,
                              void* fin_dW, void* fin_db) {
@@ -670,22 +571,15 @@ static void atb_wgrad_launch(void* stream_v, int dtype, const void** As,
   const int M = nsrc * CA;
   AtbSrc src{};
   for (int i = 0; i < nsrc && i < 4; ++i) src.a[i] = As[i];
-  hipStream_t stream = (hipStream_t)stream_v;
-  auto launch = [&](auto tptr, auto finc) {
-    using TT = std::remove_pointer_t<decltype(tptr)>;
-    constexpr bool FIN = decltype(finc)::value;
-    const AtbFin<TT> fin{fin_ticket, (TT*)fin_dW, (TT*)fin_db};
-    hipLaunchKernelGGL((atb_wgrad_kernel<TT, FIN>), grid, blk, lds, stream, src,
-                       CA, (const TT*)B, C, db, rows, M, N, fin);
-  };
-  auto by_fin = [&](auto tptr) {
-    if (fin_ticket != nullptr) launch(tptr, std::true_type{});
-    else launch(tptr, std::false_type{});
-  };
-  if (dtype == STM_BF16) by_fin((__hip_bfloat16*)nullptr);
-  else if (dtype == STM_F16) by_fin((__half*)nullptr);
-  else
-    printf("stmgcn_atb_wgrad: unsupported dtype %d (bf16/f16 only)\n", dtype);
+  stm_dispatch_lowp("stmgcn_atb_wgrad", dtype, [&](auto t) {
+    using T = decltype(t);
+    const AtbFin<T> fin{fin_ticket, (T*)fin_dW, (T*)fin_db};
+    stm_dispatch_bool(fin_ticket != nullptr, [&](auto finc) {
+      hipLaunchKernelGGL((atb_wgrad_kernel<T, decltype(finc)::value>), grid, blk,
+                         lds, (hipStream_t)stream, src, CA, (const T*)B, C, db,
+                         rows, M, N, fin);
+    });
+  });
 }
 
 extern "C" void stmgcn_atb_wgrad_multi(void* stream, int dtype, const void** As,

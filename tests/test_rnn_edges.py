@@ -1,19 +1,12 @@
 """Fused LSTM/GRU at the limits the binding allows (T = 16, L = 8), at
 T = 1, at ragged and sub-tile S, and on the eval path, against the float64
-oracle with bounds from _lowp_oracle. Plus the wave-private backward with a
-half-full last 64-row block (child process, STMGCN_BWD_WAVE=1)."""
-import os
-import subprocess
-import sys
-
+oracle with bounds from _lowp_oracle."""
 import pytest
 import torch
 
 import _lowp_oracle as lo
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda"
-WAVE_CASE = dict(S=70, T=2, L=2, cin=1)   # S_pad = 96: blocks of 64 + 32 rows
 
 
 def _to_gpu(r, grad=True):
@@ -87,29 +80,3 @@ def test_dispatcher_no_grad_and_weight_only_grad(cell):
     for i, w in enumerate(ws):
         got[f"dw{i}"] = w.grad
     r.check(got, f"dispatcher {cell} {case}", skip=("dx",))
-
-
-@pytest.mark.gpu
-def test_wave_mode_bwd_half_full_last_block():
-    """Same mechanism and bound as test_wave_mode_bwd_emits_same_layout, at
-    S = 70: the wave-private kernel's second 64-row block holds 32 rows of
-    S_pad = 96, of which 6 are live. One fresh child, STMGCN_BWD_WAVE=1."""
-    env = dict(os.environ, STMGCN_BWD_WAVE="1")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--wave-child"],
-                       env=env, cwd=REPO, capture_output=True, text=True,
-                       timeout=120)
-    print(r.stdout, r.stderr[-2000:])
-    assert r.returncode == 0, f"child exit {r.returncode}: {r.stderr[-2000:]}"
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("MAXERR ")]
-    assert len(lines) == 1, r.stdout
-    assert float(lines[0].split()[1]) < 0.08, r.stdout
-
-
-if __name__ == "__main__" and sys.argv[1:] == ["--wave-child"]:
-    sys.path.insert(0, REPO)
-    from test_rnn_wgrad_layout import _backward_rel_errors
-    assert os.environ.get("STMGCN_BWD_WAVE") == "1"
-    errs = _backward_rel_errors("lstm", **WAVE_CASE)
-    for name, e in errs.items():
-        print(name, e)
-    print("MAXERR", max(errs.values()))
