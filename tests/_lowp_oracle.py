@@ -227,6 +227,10 @@ GATE_CASES = [
     (65, 2, 8, 1),      # B > 64: two blocks of the per-batch FC kernels
     (2, 3, 2100, 1),    # N > 2048: two forward reduce chunks of 1050
     (2, 2, 300, 8),     # N*C > 2048: two backward reduce chunks
+    # the deep variant's blocks 2..n: obs is the previous block's C = 64 output
+    (2, 4, 33, 64),     # N*C = 2112: two backward chunks of 1056, split in node 16
+    (1, 16, 35, 64),    # T = 16 with C = 64
+    (2, 4, 33, 6),      # C neither 1 nor a multiple of 4
 ]
 
 
@@ -303,7 +307,8 @@ def mse_reference(n, dtype):
 
 # --------------------------------------------------------------------------
 # Seqsum: (B, T, N, C) with B*T*N = 615, not a multiple of the 256-thread block
-SEQSUM_CASES = [(3, 5, 41, C) for C in (1, 3, 4, 5)]
+# C = 64: 16 rounds of the 4-wide loop; C = 6: one round and a tail of 2
+SEQSUM_CASES = [(3, 5, 41, C) for C in (1, 3, 4, 5, 64, 6)]
 
 
 @functools.lru_cache(maxsize=None)
