@@ -405,14 +405,53 @@ extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
 // Same workgroup geometry as forward. Layers walk top-down, timesteps in
 // reverse. Per step the pointwise phase turns (dh, dc, saved gates, saved
 // cell) into gate-preactivation grads dA — lane-local in the MFMA fragment
-// layout — then two MFMA GEMMs produce dh_{t-1} (recurrent carry, kept in
-// registers) and dx_t (written to the global dh_g hand-off for the layer
-// below, or to the dx output at layer 0). dA is also streamed to global in
-// the tiled wgrad-fragment order documented in common.h (each lane's 8
-// values per gate slot are one 16 B store straight from the pointwise
-// registers); lstm_wgrad_kernel (wgrad.hip) then forms all weight gradients
-// dW = dA^T @ [h_prev | x] in one launch, which keeps this kernel lean (no
-// long-lived dW accumulators).
+// layout — then two MFMA GEMMs, run from one K loop over the shared dA
+// fragments, produce dh_{t-1} (recurrent carry, kept in registers) and dx_t
+// (written to the global dh_g hand-off for the layer below, or to the dx
+// output at layer 0). dA is also streamed to global in the tiled
+// wgrad-fragment order documented in common.h (each lane's 8 values per gate
+// slot are one 16 B store); lstm_wgrad_kernel (wgrad.hip) then forms all
+// weight gradients dW = dA^T @ [h_prev | x] in one launch, which keeps this
+// kernel lean (no long-lived dW accumulators).
+//
+// The kernel is latency-bound (two workgroups per CU, a serial dh chain), so
+// a (layer, t) stage is laid out around what each s_waitcnt has to retire;
+// vmcnt retires in issue order (profiles/lstm_bwd_stage_waits.md):
+//   layer prologue     the lane's 8 W_hh^T fragments -> its LDS slots
+//   pointwise phase    no vector-memory wait (all saves come from lane-private
+//                      LDS slots; the top layer's dout loads are the exception);
+//                      the scalar-input layer 0 reduces its dx partials (DPP)
+//   issue              W_ih^T fragments (L2), THEN the next stage's saves
+//                      (gates, c, upstream dh: HBM), THEN the dA stores
+//   barrier            dA tile visible
+//   GEMM1 + GEMM2      W_hh^T from LDS (lgkmcnt only); counted waits on W_ih^T
+//                      that leave the saves and the stores in flight
+//   dx / dh_g stores
+//   stage-in           the one wait for the saves; the stores stay in flight
+//   barrier            the next pointwise phase may overwrite the dA tile
+
+// f(std::true_type{}) or f(std::false_type{}) for a workgroup-uniform flag:
+// the device-side twin of stm_dispatch_bool
+template <typename F> __device__ __forceinline__ void rnn_uniform_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// four fp32 values rounded to T, as ONE 64-bit value (not four halves that
+// the compiler may keep in separate registers)
+template <typename T> __device__ __forceinline__ unsigned long pack4_word(f32x4 v) {
+  unsigned long w = 0;
+  #pragma unroll
+  for (int r = 0; r < 4; ++r)
+    w |= (unsigned long)__builtin_bit_cast(unsigned short, fromF<T>(v[r])) << (16 * r);
+  return w;
+}
+
+// v + (v of the lane that DPP control CTRL pairs this lane with, same row)
+template <int CTRL> __device__ __forceinline__ float dpp_row_add(float v) {
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(
+                 0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
 
 __device__ __forceinline__ int swzA(int s, int cbyte) {      // dA rows: 512 B
   return s * 512 + (cbyte ^ ((s & 15) << 4));
@@ -447,19 +486,32 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   const long S_pad = (long)gridDim.x * SEQ_TILE;
   const int hch = 16 * wv + l16;
 
-  // LDS holds only the dA tiles (ping/pong by timestep parity: the pointwise
-  // writes of step t never alias the buffer step t+1's GEMMs/stream read, so
-  // the loop-top WAR barrier drops) + the CIN1 dx reduction scratch. The
-  // cross-layer dh hand-off lives in GLOBAL scratch dh_g — dropping the
-  // [Tst] dh slots cuts LDS from ~64.5 KB (2 WGs/CU) to ~32.5 KB (4 WGs/CU),
-  // doubling the occupancy that hides the serial BPTT latency.
-  char* dA_buf0 = lds;                        // [SEQ_TILE][512B] swizzled
-  char* dA_buf1 = dA_buf0 + SEQ_TILE * 512;
-  float* red = (float*)(dA_buf1 + SEQ_TILE * 512);  // [4][SEQ_TILE] cross-wave scratch
+  // LDS, 76.5 KB, two workgroups per CU (the register allocation allows no
+  // more): ONE dA tile (the barrier at the end of a stage keeps the next
+  // pointwise phase from overwriting it under a wave that still reads it),
+  // the CIN1 dx reduction scratch, the lane-private parking of the saves and
+  // the layer's W_hh^T. The cross-layer dh hand-off lives in GLOBAL scratch
+  // dh_g.
+  char* dA_lds = lds;                         // [SEQ_TILE][512B] swizzled
+  float* red = (float*)(dA_lds + SEQ_TILE * 512);   // [4][SEQ_TILE] cross-wave scratch
   // lane-PRIVATE gates staging (each lane writes exactly the 2*MT fragments
   // it alone reads next stage -> no cross-wave visibility, no barrier, and
   // the prefetched tile costs LDS instead of 32 live VGPRs)
   char* gstage = (char*)(red + 4 * SEQ_TILE);       // [256][MT*32B]
+  // lane-private packed saves, parked the same way: the upstream dh words of
+  // the stage ([256][MT*8B]) and the cell words by timestep parity
+  // ([2][256][MT*8B]: stage t reads c_t from slot t&1 and c_{t-1} from the
+  // other, and its prefetched c_{t-2} replaces the dead c_t, so nothing
+  // rotates). They go from the load's registers to LDS untouched.
+  char* dhstage = gstage + 256 * (MT * 32);
+  char* cstage = dhstage + 256 * (MT * 8);
+  // W_hh^T of the current layer in B-fragment order, [kk][256 lanes][16 B]:
+  // every lane stages, once per layer, exactly the 8 fragments it reads in
+  // each stage (lane-private like the slots above: no barrier), so GEMM1 —
+  // the GEMM on the serial dh chain — waits on lgkmcnt only and its weights
+  // are off the vector-memory queue. A wave's ds_read_b128 is 1 KiB contiguous.
+  char* wstage = cstage + 2 * 256 * (MT * 8);
+  char* wmine = wstage + threadIdx.x * 16;
 
   for (int layer = L - 1; layer >= 0; --layer) {
     const bool l0cin1 = CIN1 && layer == 0;
@@ -471,90 +523,130 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       #pragma unroll
       for (int r = 0; r < 4; ++r) { dh_rec[m][r] = 0.f; dc[m][r] = 0.f; }
 
-    // ---- training-save prefetch pipeline: gates/cseq for step t are
-    // loaded during step t+1's GEMM phase (the kernel is latency-bound at
-    // 2 WGs/CU; these are the only global loads in the hot loop) ----------
+    // ---- training-save prefetch pipeline: gates/cseq (and the upstream dh)
+    // for step t are loaded during stage t+1 and parked in the lane's LDS
+    // slots at its end; the layer prologue fills the slots for the first
+    // stage ----------------------------------------------------------------
     const long lay_base = (long)layer * Tst;
+    // (the *_at pointers are workgroup-uniform tile bases; the lane's place
+    // in the tile is the small offset lane_frag(m), so that one offset
+    // register serves every save instead of a 64-bit address each)
+    auto lane_frag = [&](int m) -> unsigned { return (wv * MT + m) * 64 + lane; };
     auto g_at = [&](int t) {
       return gates_g + (lay_base + t) * (S_pad * 4 * RNN_H)
-             + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H) + (wv * MT) * 64 * 16;
+             + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H);
     };
     auto c_at = [&](int t) {
       return cseq_g + (lay_base + t) * (S_pad * RNN_H)
-             + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
+             + (long)blockIdx.x * (SEQ_TILE * RNN_H);
     };
     // dh hand-off is FRAG-NATIVE: the GEMM2 writer and the pointwise reader
     // use the identical lane mapping (row 16m+4lgrp+r, col hch), so each
     // lane stores/loads its 4 values as one packed 8-byte word.
     auto dh_at = [&](int t) {
       return dh_g + (long)t * (S_pad * RNN_H)
-             + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
+             + (long)blockIdx.x * (SEQ_TILE * RNN_H);
     };
     char* gmine = gstage + threadIdx.x * (MT * 32);
     #pragma unroll
     for (int m = 0; m < MT; ++m) {
       *(frag*)&gmine[m * 32 + 0] =
-          *(((const frag*)(g_at(Tst - 1) + (m * 64 + lane) * 16)) + 0);
+          *(((const frag*)(g_at(Tst - 1) + lane_frag(m) * 16)) + 0);
       *(frag*)&gmine[m * 32 + 16] =
-          *(((const frag*)(g_at(Tst - 1) + (m * 64 + lane) * 16)) + 1);
+          *(((const frag*)(g_at(Tst - 1) + lane_frag(m) * 16)) + 1);
     }
     // upstream dh (layer above) for step t, prefetched one stage ahead so
     // the global loads never sit at the top of the pointwise critical path
-    ulong1 dhup[MT];
+    ulong1* dhmine = (ulong1*)(dhstage + threadIdx.x * (MT * 8));
+    auto cmine = [&](int t) {
+      return (ulong1*)(cstage + ((t & 1) * 256 + threadIdx.x) * (MT * 8));
+    };
     if (layer < L - 1) {
       #pragma unroll
       for (int m = 0; m < MT; ++m)
-        dhup[m] = *(const ulong1*)(dh_at(Tst - 1) + (m * 64 + lane) * 4);
+        dhmine[m] = *(const ulong1*)(dh_at(Tst - 1) + lane_frag(m) * 4);
     }
-    // c rotation: stage t consumes c_t and c_{t-1}; the next stage reuses
-    // c_{t-1} as ITS c_t, so only ONE new (prefetched) c load per stage.
-    ulong1 cc_t[MT], cc_p[MT];
+    // stage t consumes c_t and c_{t-1}; the next stage reuses c_{t-1} as ITS
+    // c_t, so only ONE new (prefetched) c load per stage.
     #pragma unroll
     for (int m = 0; m < MT; ++m) {
-      cc_t[m] = *(const ulong1*)(c_at(Tst - 1) + (m * 64 + lane) * 4);
-      cc_p[m] = ulong1{0};
+      cmine(Tst - 1)[m] = *(const ulong1*)(c_at(Tst - 1) + lane_frag(m) * 4);
       if (!GRU && Tst >= 2)
-        cc_p[m] = *(const ulong1*)(c_at(Tst - 2) + (m * 64 + lane) * 4);
+        cmine(Tst - 2)[m] = *(const ulong1*)(c_at(Tst - 2) + lane_frag(m) * 4);
     }
-    // layer boundary: dA-buffer parity reuse needs the readers done, and
+    // this lane's row of W_hh^T -> its LDS slots (read back in every stage)
+    {
+      const unsigned wl = (hch * (4 * RNN_H) + lgrp * 8) * sizeof(T);
+      #pragma unroll
+      for (int kk = 0; kk < 8; ++kk)
+        *(frag*)&wmine[kk * 4096] = *(const frag*)((const char*)WhhT + (wl + kk * 64));
+    }
+    // scalar-input layer 0: this lane's four W_ih values, once per layer
+    float wih0[4];
+    if (l0cin1) {
+      #pragma unroll
+      for (int q = 0; q < 4; ++q) wih0[q] = toF<T>(WihT[q * 64 + hch]);
+    }
+    // layer boundary: the dA tile's readers of the last stage must be done, and
     // this block's dh_g stores must be visible to its next-layer loads
     __threadfence_block();
     __syncthreads();
 
-    for (int t = Tst - 1; t >= 0; --t) {
-      char* dA_lds = (t & 1) ? dA_buf1 : dA_buf0;
+    unsigned long dh_sent[MT] = {};   // the words last stored to dh_g (see stage_rest)
+    #pragma clang loop unroll(disable)   // no peeled first stage either
+    for (int t = Tst - 1;; --t) {
       const long base = lay_base + t;
 
-      float wih0[4];
-      if (l0cin1) {
-        #pragma unroll
-        for (int q = 0; q < 4; ++q) wih0[q] = toF<T>(WihT[q * 64 + hch]);
-      }
       float dxpart[MT][4];
       // this lane's dA values, packed in stream order: slot q, k' - 8*lgrp =
       // 4*m + r (common.h) -> one 16 B piece per gate slot
       alignas(16) T pk[4][MT * 4];
 
+      // top layer: the lane's 8 dout values, loaded back to back and waited
+      // for once. Tail rows load the tile's last valid row (always in bounds)
+      // and are masked by a select below, not by a branch around the load.
+      const bool top_dout = layer == L - 1 && (ret_seq || t == Tst - 1);
+      T dov[MT][4];
+      if (top_dout) {
+        // workgroup-uniform tile base + small per-lane offsets
+        const int dstride = ret_seq ? Tst * RNN_H : RNN_H;
+        const T* dtile = dout + (long)s0 * dstride + (ret_seq ? t * RNN_H : 0);
+        const int last = S - 1 - s0;
+        // (the empty asm keeps the 8 offsets from being carried in registers
+        // through the whole kernel for a load that most stages do not issue)
+        int row0 = 4 * lgrp;
+        asm volatile("" : "+v"(row0));
+        #pragma unroll
+        for (int m = 0; m < MT; ++m)
+          #pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = 16 * m + row0 + r;
+            dov[m][r] = dtile[(row < last ? row : last) * dstride + hch];
+          }
+      }
+
       #pragma unroll
       for (int m = 0; m < MT; ++m) {
         frag gf0 = *(const frag*)&gmine[m * 32 + 0];                 // i|f
         frag gf1 = *(const frag*)&gmine[m * 32 + 16];                // g|o
+        const ulong1 cc_t = cmine(t)[m];
+        const ulong1 cc_p = (!GRU && t > 0) ? cmine(t - 1)[m] : ulong1{0};
+        ulong1 dhup = ulong1{0};
+        if (layer < L - 1) dhup = dhmine[m];
         f32x4 ct, cpv;
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          ct[r] = elemF(((elem*)&cc_t[m])[r]);
-          cpv[r] = (t > 0) ? elemF(((elem*)&cc_p[m])[r]) : 0.f;
+          ct[r] = elemF(((const elem*)&cc_t)[r]);
+          cpv[r] = elemF(((const elem*)&cc_p)[r]);
         }
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = 16 * m + 4 * lgrp + r;
           float dh = dh_rec[m][r];
           if (layer < L - 1) {
-            dh += elemF(((elem*)&dhup[m])[r]);
-          } else if (ret_seq) {
-            if (s0 + row < S) dh += toF<T>(dout[((long)(s0 + row) * Tst + t) * RNN_H + hch]);
-          } else if (t == Tst - 1) {
-            if (s0 + row < S) dh += toF<T>(dout[(long)(s0 + row) * RNN_H + hch]);
+            dh += elemF(((const elem*)&dhup)[r]);
+          } else if (top_dout) {
+            dh = (s0 + row < S) ? dh + toF<T>(dov[m][r]) : dh;
           }
           float dAi, dAf, dAg, dAo;
           if (GRU) {
@@ -602,129 +694,212 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       // stored after the GEMMs. A store issued here would be drained by GEMM1's
       // first weight-fragment wait (vmcnt retires in order) on the serial
       // dh_prev path: ~1% slower, profiles/r03_da_stream_layout.md.
-      T* out_dA = dA_g + stm_da_tile_off(base * S_pad + s0);
-      #pragma unroll
-      for (int q = 0; q < 4; ++q) *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
-      __syncthreads();   // dA visible to all waves
-
-      // prefetch next stage's saves (overlap the GEMMs below). The gate
-      // loads issue NOW but their LDS stage-in happens at the END of the
-      // stage: a ds_write forces a vector-memory wait on its operand, and
-      // doing that here would drain the dA stream stores of the previous
-      // stage too (full HBM store latency exposed every stage — the 70%
-      // wave-park of round 1). c_{t-2} and dh go to packed registers.
-      ulong1 dhnext[MT], cnext[MT];
-      frag gld[MT][2];
-      if (t > 0) {
-        #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          gld[m][0] = *(((const frag*)(g_at(t - 1) + (m * 64 + lane) * 16)) + 0);
-          gld[m][1] = *(((const frag*)(g_at(t - 1) + (m * 64 + lane) * 16)) + 1);
-        }
-        // LSTM rotates c_{t-1} into c_t, so only c_{t-2} is new; GRU's
-        // save is h_{t-1} (no reuse), so its next stage needs c_at(t-1)
-        if (GRU || t >= 2) {
-          #pragma unroll
-          for (int m = 0; m < MT; ++m)
-            cnext[m] = *(const ulong1*)(c_at(GRU ? t - 1 : t - 2)
-                                        + (m * 64 + lane) * 4);
-        }
-        if (layer < L - 1) {
-          #pragma unroll
-          for (int m = 0; m < MT; ++m)
-            dhnext[m] = *(const ulong1*)(dh_at(t - 1) + (m * 64 + lane) * 4);
-        }
-      }
-
-      // ---- GEMM1: dh_prev = dA @ W_hh ------------------------------------
-      if (t > 0) {
-        f32x4 acc[MT];
-        #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        #pragma unroll 4
-        for (int kk = 0; kk < 8; ++kk) {
-          frag b = *(const frag*)&WhhT[hch * (4 * RNN_H) + kk * 32 + lgrp * 8];
-          #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            frag a = *(const frag*)&dA_lds[swzA(16 * m + l16, (kk * 32 + lgrp * 8) * 2)];
-            acc[m] = mfma16x16x32(a, b, acc[m]);
-          }
-        }
+      if (l0cin1) {
+        // CIN1 l0: dx[s,t] = sum_g dA[s,g] W_ih[g,0], reduced here so that
+        // the dA barrier below also publishes the per-wave sums. The 16 lanes of an l16
+        // group are one DPP row: quad_perm pairs lanes xor 1 and xor 2, then
+        // row_half_mirror / row_mirror pair lanes whose quads already hold
+        // equal sums — the pairing tree of an xor butterfly, without LDS
+        // permutes. The 8 values are independent chains.
         #pragma unroll
         for (int m = 0; m < MT; ++m)
           #pragma unroll
-          for (int r = 0; r < 4; ++r) dh_rec[m][r] = acc[m][r];
-      }
-
-      // ---- GEMM2: dx = dA @ W_ih -> dh_g step t / dx output --------------
-      if (!l0cin1) {
-        f32x4 acc[MT];
+          for (int r = 0; r < 4; ++r) dxpart[m][r] = dpp_row_add<0xB1>(dxpart[m][r]);
         #pragma unroll
-        for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        #pragma unroll 4
-        for (int kk = 0; kk < 8; ++kk) {
-          frag b = *(const frag*)&WihT[hch * (4 * RNN_H) + kk * 32 + lgrp * 8];
+        for (int m = 0; m < MT; ++m)
           #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            frag a = *(const frag*)&dA_lds[swzA(16 * m + l16, (kk * 32 + lgrp * 8) * 2)];
-            acc[m] = mfma16x16x32(a, b, acc[m]);
-          }
-        }
-        if (layer > 0) {
+          for (int r = 0; r < 4; ++r) dxpart[m][r] = dpp_row_add<0x4E>(dxpart[m][r]);
+        #pragma unroll
+        for (int m = 0; m < MT; ++m)
           #pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            T v4[4];
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) v4[r] = fromF<T>(acc[m][r]);
-            *(ulong1*)(dh_at(t) + (m * 64 + lane) * 4) = *(ulong1*)v4;
-          }
-        } else {
-          #pragma unroll
-          for (int m = 0; m < MT; ++m)
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int row = 16 * m + 4 * lgrp + r;
-              if (s0 + row < S)
-                dx[((long)(s0 + row) * Tst + t) * RNN_H + hch] = fromF<T>(acc[m][r]);
-            }
-        }
-      } else {
-        // CIN1 l0: dx[s,t] = sum_g dA[s,g] W_ih[g,0]
+          for (int r = 0; r < 4; ++r) dxpart[m][r] = dpp_row_add<0x141>(dxpart[m][r]);
         #pragma unroll
         for (int m = 0; m < MT; ++m)
           #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            float v = dxpart[m][r];
-            #pragma unroll
-            for (int off = 1; off < 16; off <<= 1) v += __shfl_xor(v, off, 64);
+            const float v = dpp_row_add<0x140>(dxpart[m][r]);
             if (l16 == 0) red[wv * SEQ_TILE + 16 * m + 4 * lgrp + r] = v;
           }
-        __syncthreads();
-        if (wv == 0) {
-          for (int sA = lane; sA < SEQ_TILE; sA += 64) {
-            const float v = red[sA] + red[SEQ_TILE + sA] + red[2 * SEQ_TILE + sA] + red[3 * SEQ_TILE + sA];
-            if (s0 + sA < S) dx[(long)(s0 + sA) * Tst + t] = fromF<T>(v);
-          }
-        }
       }
-
-      // ---- stream the parked dA pieces to global (4 x ds_read_b128 of the
-      // lane's own slot; no cross-lane traffic, no barrier) ------------------
+      T* out_dA = dA_g + stm_da_tile_off(base * S_pad + s0);
       #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *(frag*)&out_dA[stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
-            *(const frag*)&gmine[q * 16];
-
-      if (t > 0) {
+      for (int q = 0; q < 4; ++q) *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
+      // ---- the rest of the stage, one straight-line body per combination of
+      // the workgroup-uniform conditions (REC: t > 0, a recurrent GEMM and a
+      // next stage exist; INP: the layer has an input GEMM, all but the
+      // scalar-input layer 0; UP: a layer above hands dh down), so that every
+      // wait in it is counted against loads that are certainly in flight.
+      //
+      // dgrad GEMMs: dh_prev = dA @ W_hh (GEMM1) and dx = dA @ W_ih (GEMM2)
+      // from ONE K loop. Both read the same 16 A fragments of the dA tile, so
+      // each is read once and feeds both accumulator chains (each still sums
+      // kk = 0..7 in order). GEMM1's weights come from the lane's LDS slots;
+      // GEMM2's eight fragments are the only weights on the vector-memory
+      // queue and are requested first, before the barrier.
+      //
+      // The next stage's saves (gates, c, upstream dh) are prefetched from HBM
+      // right behind them, also before the barrier: vmcnt retires in order, so
+      // a save load in front of a weight load would make that weight's wait
+      // pay the HBM latency. The words go to their lane-private LDS slots
+      // untouched at the end of the stage, the one place that waits for them;
+      // the dA stores are issued right behind them, the dx / dh_g stores after
+      // the GEMMs, and neither is waited for.
+      auto stage_rest = [&](auto rec_c, auto inp_c, auto up_c) {
+        constexpr bool REC = decltype(rec_c)::value;
+        constexpr bool INP = decltype(inp_c)::value;
+        constexpr bool UP = decltype(up_c)::value;
+        // row hch of W_ih^T, as a 32-bit byte offset from the uniform pointer
+        const unsigned wlane = (hch * (4 * RNN_H) + lgrp * 8) * sizeof(T);
+        frag b2[2][4];
+        f32x4 acc1[MT], acc2[MT];
         #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          *(frag*)&gmine[m * 32 + 0] = gld[m][0];   // loads landed long ago
-          *(frag*)&gmine[m * 32 + 16] = gld[m][1];
-          cc_t[m] = GRU ? cnext[m] : cc_p[m];
-          if (!GRU) cc_p[m] = (t >= 2) ? cnext[m] : ulong1{0};
-          if (layer < L - 1) dhup[m] = dhnext[m];
+          acc1[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+          acc2[m] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+        auto mfma_half = [&](int h) {   // k-steps 4h .. 4h+3 of both GEMMs
+          frag b1[4];
+          if constexpr (REC) {
+            #pragma unroll
+            for (int j = 0; j < 4; ++j) b1[j] = *(const frag*)&wmine[(4 * h + j) * 4096];
+          }
+          if constexpr (REC || INP) {
+            #pragma unroll
+            for (int jb = 0; jb < 4; jb += 2) {
+              frag a[2][MT];
+              #pragma unroll
+              for (int j = 0; j < 2; ++j)
+                #pragma unroll
+                for (int m = 0; m < MT; ++m)
+                  a[j][m] = *(const frag*)&dA_lds[swzA(16 * m + l16, ((4 * h + jb + j) * 32 + lgrp * 8) * 2)];
+              #pragma unroll
+              for (int j = 0; j < 2; ++j)
+                #pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                  if constexpr (REC) acc1[m] = mfma16x16x32(a[j][m], b1[jb + j], acc1[m]);
+                  if constexpr (INP) acc2[m] = mfma16x16x32(a[j][m], b2[h][jb + j], acc2[m]);
+                }
+            }
+          }
+        };
+        // The compiler waits (vmcnt) before it overwrites the data registers
+        // of a store still in flight, and the previous stage's dh_g store is
+        // the youngest thing in the queue: reusing its registers at the top of
+        // the pointwise phase drained the whole queue there. Naming them here
+        // keeps them untouched until the store has had a pointwise phase to
+        // retire.
+        if constexpr (INP) {
+          #pragma unroll
+          for (int m = 0; m < MT; ++m) asm volatile("" :: "v"(dh_sent[m]));
+        }
+        if constexpr (INP) {
+          #pragma unroll
+          for (int kk = 0; kk < 8; ++kk)
+            b2[kk / 4][kk % 4] = *(const frag*)((const char*)WihT + (wlane + kk * 64));
+        }
+        ulong1 dhnext[MT], cnext[MT];
+        frag gld[MT][2];
+        if constexpr (REC) {
+          __builtin_amdgcn_sched_barrier(0);
+          #pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            gld[m][0] = *(((const frag*)(g_at(t - 1) + lane_frag(m) * 16)) + 0);
+            gld[m][1] = *(((const frag*)(g_at(t - 1) + lane_frag(m) * 16)) + 1);
+          }
+          // LSTM rotates c_{t-1} into c_t, so only c_{t-2} is new (at t == 1
+          // nothing is: the load repeats c_0 and is dropped); GRU's save is
+          // h_{t-1} (no reuse), so its next stage needs c_at(t-1)
+          const int tc = GRU ? t - 1 : (t >= 2 ? t - 2 : 0);
+          #pragma unroll
+          for (int m = 0; m < MT; ++m)
+            cnext[m] = *(const ulong1*)(c_at(tc) + lane_frag(m) * 4);
+          if constexpr (UP) {
+            #pragma unroll
+            for (int m = 0; m < MT; ++m)
+              dhnext[m] = *(const ulong1*)(dh_at(t - 1) + lane_frag(m) * 4);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // ---- stream the parked dA pieces to global (4 x ds_read_b128 of the
+        // lane's own slot; no cross-lane traffic), behind every load of the
+        // stage: no wait below has to retire them, and they get the rest of
+        // the stage before the next pointwise phase reuses their registers ---
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *(frag*)&out_dA[(unsigned)stm_da_elem(q * RNN_H + hch, 8 * lgrp)] =
+              *(const frag*)&gmine[q * 16];
+
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();   // dA (and the layer-0 dx partials) visible to all waves
+        mfma_half(0);
+        mfma_half(1);
+        if constexpr (REC) {
+          #pragma unroll
+          for (int m = 0; m < MT; ++m)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) dh_rec[m][r] = acc1[m][r];
+        }
+
+        // ---- dx -> dh_g step t (layer hand-off) / dx output ---------------
+        if constexpr (INP) {
+          if (layer > 0) {
+            #pragma unroll
+            for (int m = 0; m < MT; ++m) {
+              dh_sent[m] = pack4_word<T>(acc2[m]);
+              *(unsigned long*)(dh_at(t) + lane_frag(m) * 4) = dh_sent[m];
+            }
+          } else {
+            // workgroup-uniform row pointers + one lane offset for all 8
+            T* dxtile = dx + ((long)s0 * Tst + t) * RNN_H;
+            const unsigned dxlane = 4 * lgrp * (Tst * RNN_H) + hch;
+            #pragma unroll
+            for (int m = 0; m < MT; ++m)
+              #pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int row = 16 * m + 4 * lgrp + r;
+                if (s0 + row < S)
+                  (dxtile + (16 * m + r) * (Tst * RNN_H))[dxlane] = fromF<T>(acc2[m][r]);
+              }
+          }
+        } else {
+          // CIN1 l0: the cross-wave sum of the partials reduced before the barrier
+          if (wv == 0) {
+            for (int sA = lane; sA < SEQ_TILE; sA += 64) {
+              const float v = red[sA] + red[SEQ_TILE + sA] + red[2 * SEQ_TILE + sA] + red[3 * SEQ_TILE + sA];
+              if (s0 + sA < S) dx[(long)(s0 + sA) * Tst + t] = fromF<T>(v);
+            }
+          }
+        }
+
+        // ---- stage-in: the stage's one wait on the save prefetch -----------
+        if constexpr (REC) {
+          #pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            *(frag*)&gmine[m * 32 + 0] = gld[m][0];
+            *(frag*)&gmine[m * 32 + 16] = gld[m][1];
+            // LSTM: c_{t-2} replaces the dead c_t, same parity (at t == 1 the
+            // repeated c_0 lands in the dead c_1 slot, which nobody reads)
+            cmine(GRU ? t - 1 : t)[m] = cnext[m];
+            if constexpr (UP) dhmine[m] = dhnext[m];
+          }
+          __syncthreads();   // the next pointwise phase overwrites dA / red
+        }
+      };
+      auto stage_rest_for = [&](auto rec_c) {
+        rnn_uniform_bool(!l0cin1, [&](auto inp_c) {
+          rnn_uniform_bool(layer < L - 1, [&](auto up_c) {
+            stage_rest(rec_c, inp_c, up_c);
+          });
+        });
+      };
+      // The last stage leaves the loop on its own edge: its dA stores are
+      // still in flight, and if that state reached the loop header every
+      // stage would drain its stores at the top.
+      if (t == 0) {
+        stage_rest_for(std::false_type{});
+        break;
       }
+      stage_rest_for(std::true_type{});
     }  // t loop
   }  // layer loop
 }
@@ -737,12 +912,18 @@ extern "C" void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout,
                                 int ret_seq, int gru) {
   const RnnPtrs p = rnn_ptrs(L, w_ihT, w_hhT, nullptr, nullptr);
   const int nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
-  // two dA tiles + the CIN1 dx reduction scratch + the lane-private gstage
-  const size_t lds_bytes = 2 * SEQ_TILE * 512 + 4 * SEQ_TILE * sizeof(float)
-                           + 256 * (SEQ_TILE / 16) * 32;
+  // the dA tile + the CIN1 dx reduction scratch + the lane-private parking of
+  // the saves (gates 32 B per m-tile, dh and two cell parities 8 B each) +
+  // W_hh^T of one layer: 76.5 KB, above the 64 KB a launch gets unasked
+  const size_t lds_bytes = SEQ_TILE * 512 + 4 * SEQ_TILE * sizeof(float)
+                           + 256 * (SEQ_TILE / 16) * (32 + 3 * 8)
+                           + RNN_H * 4 * RNN_H * 2;
   stm_dispatch_lowp("stmgcn_lstm_bwd", dtype, [&](auto t) {
     using T = decltype(t);
     rnn_dispatch_variant(cin, gru, [&](auto cin1, auto is_gru) {
+      STM_CHECK_HIP(hipFuncSetAttribute(
+          (const void*)lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>,
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
       hipLaunchKernelGGL(
           (lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>),
           dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)dout,
