@@ -86,9 +86,26 @@ __device__ __forceinline__ float stm_sigmoid(float x) {
   return __builtin_amdgcn_rcpf(1.0f + __expf(-x));
 }
 __device__ __forceinline__ float stm_tanh(float x) {
-  // tanh(x) = 2*sigmoid(2x) - 1; clamp keeps exp finite for large |x|
-  const float t = (x > 15.f) ? 15.f : (x < -15.f ? -15.f : x);
-  return fmaf(2.0f, stm_sigmoid(2.0f * t), -1.0f);
+  // tanh(x) = 2*sigmoid(2x) - 1, the 2 of 2x folded into the exponent's
+  // constant (a power of two: the product keeps its bits). No clamp: where
+  // exp2 underflows to 0 or overflows to inf, rcp gives 1 or 0 and the fma
+  // exactly +-1, which is what every |x| > 9.1 rounds to anyway; NaN stays NaN.
+  const float e = __builtin_amdgcn_exp2f(x * (-2.0f * 0x1.715476p+0f));
+  return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + e), -1.0f);
+}
+
+// One separately rounded fp32 product / sum: never contracted into an FMA with
+// a neighbour, whatever the surrounding code looks like (HIP contracts a * b + c
+// by default, and which of two products it fuses depends on the context).
+// Where a kernel's results are pinned bit for bit, its pointwise arithmetic is
+// written with these and fmaf.
+__device__ __forceinline__ float stm_fmul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float stm_fadd(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
 }
 
 // LDS swizzle for 128-byte tile rows (64 bf16/f16 channels): element (row s,

@@ -70,6 +70,13 @@ extern "C" __global__ void mfma_probe_kernel(const __hip_bfloat16* A,
       for (int r = 0; r < 4; ++r) D[((l / 16) * 4 + r) * 16 + (l % 16)] = c[r];
 }
 
+// f(std::true_type{}) or f(std::false_type{}) for a workgroup-uniform flag:
+// the device-side twin of stm_dispatch_bool
+template <typename F> __device__ __forceinline__ void rnn_uniform_bool(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 // ---------------------------------------------------------------------------
 // Fused LSTM/GRU forward.
 //
@@ -106,6 +113,8 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
                 RnnPtrs ptrs,
                 int S, int Tst, int L, int ret_seq) {
   using frag = typename Frag8<T>::type;
+  using elem = typename Frag8<T>::elem;
+  typedef elem elem4 __attribute__((ext_vector_type(4)));
   constexpr int MT = SEQ_TILE / 16;        // MFMA row-tiles per wave
   constexpr int SLOT = SEQ_TILE * 128;     // one timestep LDS slot, bytes
   extern __shared__ char lds[];
@@ -133,49 +142,35 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
   }
 
   const int hch = 16 * wv + l16;                      // this lane's h channel
+  // The lane's part of every global address, as small byte offsets; what is
+  // added to them per layer and stage is workgroup-uniform (one offset
+  // register serves all fragments of a stream instead of a 64-bit address each)
+  const unsigned wlane = (hch * RNN_H + lgrp * 8) * sizeof(T);      // weight row hch
+  const unsigned inlane = (l16 * RNN_H + lgrp * 8) * sizeof(T);     // hseq rows as A fragments
+  const unsigned savelane = (wv * MT * 64 + lane) * sizeof(T);      // fragment-native saves
 
-  for (int layer = 0; layer < L; ++layer) {
-    const T* Whh = (const T*)ptrs.w_hh[layer];
-    const T* Wih = (const T*)ptrs.w_ih[layer];
+  // One layer: a straight-line body per combination of the workgroup-uniform
+  // conditions FIRST (layer 0: the scalar-input layer of a cin = 1 model has
+  // no input GEMM and adds its rank-1 input term in the pointwise phase; a
+  // dense layer 0 reads x, guarded, instead of the hand-off), TRAIN (the
+  // gates / cell saves exist) and TOP (the layer that writes `out`). A stage
+  // then holds no code of another form: the kernel is bound by instruction
+  // issue in its pointwise phase (profiles/lstm_fwd_stage.md).
+  auto layer_body = [&](int layer, auto first_c, auto train_c, auto top_c) {
+    constexpr bool FIRST = decltype(first_c)::value;
+    constexpr bool TRAIN = decltype(train_c)::value;
+    constexpr bool TOP = decltype(top_c)::value;
+    constexpr bool SCALAR = CIN1 && FIRST;
+    constexpr bool KEEP_H = TRAIN || !TOP;   // the top layer's sequence is dead in eval
+    const char* Whh = (const char*)ptrs.w_hh[layer];
+    const char* Wih = (const char*)ptrs.w_ih[layer];
     const T* bih = (const T*)ptrs.b_ih[layer];
     const T* bhh = (const T*)ptrs.b_hh[layer];
 
-    // B-fragments for the recurrent GEMM: b_hh[q][kk]; W row g = q*64 + hch,
-    // cols kk*32 + lgrp*8 .. +8 -> contiguous 16B in the (4H, H) weight.
-    frag bhfrag[4][2];
-    #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      #pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        bhfrag[q][kk] = *(const frag*)&Whh[(q * 64 + hch) * RNN_H + kk * 32 + lgrp * 8];
-    // input-projection B-fragments (dense layers only)
-    frag bxfrag[4][2];
-    if (!CIN1 || layer > 0)
-      #pragma unroll
-      for (int q = 0; q < 4; ++q)
-        #pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-          bxfrag[q][kk] = *(const frag*)&Wih[(q * 64 + hch) * RNN_H + kk * 32 + lgrp * 8];
-    // layer-0 scalar input weights (CIN1): W_ih[g][0]
-    float wih0[4];
-    float bias[4];
-    #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int g = q * 64 + hch;
-      bias[q] = toF<T>(bih[g]) + toF<T>(bhh[g]);
-      if (CIN1 && layer == 0) wih0[q] = toF<T>(Wih[g]);
-    }
-
-    // previous layer's output sequence (global hand-off)
-    const T* hin = (layer > 0)
-        ? hseq_g + ((long)(layer - 1) * Tst) * (S_pad * RNN_H)
-        : nullptr;
-
-    float c_state[MT][4];  // [m][reg]
-    #pragma unroll
-    for (int m = 0; m < MT; ++m)
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) c_state[m][r] = 0.f;
+    // previous layer's output sequence (global hand-off; L2-hot: this block
+    // wrote the same tile last layer), or the dense x of layer 0
+    const T* hin = FIRST ? nullptr
+        : hseq_g + ((long)(layer - 1) * Tst) * (S_pad * RNN_H) + (long)s0 * RNN_H;
 
     // input-term fragments, prefetched one stage ahead (single-buffered:
     // reloaded right after their MFMAs consume them, so the global loads
@@ -184,29 +179,63 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
     auto load_input = [&](int t) {
       #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        const int row = 16 * m + l16;
         #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-          if (layer == 0) {            // dense x (S, Tst, 64): guard the tail
+          if constexpr (FIRST) {       // dense x (S, Tst, 64): guard the tail
+            const char* xt = (const char*)(x + ((long)(s0 + 16 * m) * Tst + t) * RNN_H);
+            const unsigned xlane = (l16 * Tst * RNN_H + lgrp * 8) * sizeof(T);
             xfr[m][kk] = frag{};
-            if (s0 + row < S)
-              xfr[m][kk] = *(const frag*)&x[((long)(s0 + row) * Tst + t) * RNN_H + kk * 32 + lgrp * 8];
+            if (s0 + 16 * m + l16 < S)
+              xfr[m][kk] = *(const frag*)(xt + (xlane + kk * 32 * sizeof(T)));
           } else {
-            xfr[m][kk] = *(const frag*)&hin[((long)t * S_pad + s0 + row) * RNN_H + kk * 32 + lgrp * 8];
+            const char* ht = (const char*)(hin + (long)t * (S_pad * RNN_H));
+            xfr[m][kk] = *(const frag*)(ht + (inlane + (m * 16 * RNN_H + kk * 32) * sizeof(T)));
           }
         }
       }
     };
-    if (!CIN1 || layer > 0) load_input(0);
+    if constexpr (!SCALAR) load_input(0);
 
+    // B-fragments for the recurrent GEMM: b_hh[q][kk]; W row g = q*64 + hch,
+    // cols kk*32 + lgrp*8 .. +8 -> contiguous 16B in the (4H, H) weight.
+    frag bhfrag[4][2];
+    #pragma unroll
+    for (int q = 0; q < 4; ++q)
+      #pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+        bhfrag[q][kk] = *(const frag*)(Whh + (wlane + (q * 64 * RNN_H + kk * 32) * sizeof(T)));
+    // input-projection B-fragments (layers with an input GEMM)
+    frag bxfrag[4][2];
+    if constexpr (!SCALAR) {
+      #pragma unroll
+      for (int q = 0; q < 4; ++q)
+        #pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+          bxfrag[q][kk] = *(const frag*)(Wih + (wlane + (q * 64 * RNN_H + kk * 32) * sizeof(T)));
+    }
+    // scalar-input layer: W_ih[g][0]
+    float wih0[4];
+    float bias[4];
+    #pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int g = q * 64 + hch;
+      bias[q] = toF<T>(bih[g]) + toF<T>(bhh[g]);
+      if constexpr (SCALAR) wih0[q] = toF<T>(((const T*)Wih)[g]);
+    }
+
+    float c_state[MT][4];  // [m][reg]
+    #pragma unroll
+    for (int m = 0; m < MT; ++m)
+      #pragma unroll
+      for (int r = 0; r < 4; ++r) c_state[m][r] = 0.f;
+
+    #pragma clang loop unroll(disable)   // no peeled first or last stage
     for (int t = 0; t < Tst; ++t) {
       f32x4 acc[MT][4];  // [m][q]
-      #pragma unroll
-      for (int m = 0; m < MT; ++m)
-        #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[m][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-      // recurrent term: h_{t-1} from the previous parity slot (zero at t==0)
+      // recurrent term: h_{t-1} from the previous parity slot (zero at t==0);
+      // the first MFMA of a chain takes the constant 0 as its accumulator
       if (t > 0) {
         char* slot = hslot(t - 1);
         #pragma unroll
@@ -217,14 +246,23 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
             frag a = *(const frag*)&slot[lds_swz(row, (kk * 32 + lgrp * 8) * 2)];
             #pragma unroll
             for (int q = 0; q < 4; ++q)
-              acc[m][q] = mfma16x16x32(a, bhfrag[q][kk], acc[m][q]);
+              acc[m][q] = mfma16x16x32(a, bhfrag[q][kk], kk == 0 ? zero4 : acc[m][q]);
           }
         }
+      } else {
+        // (the empty asm keeps this a block of its own: without it the 32
+        // zero moves are hoisted in front of the branch, into every stage.
+        // Speed only, and seen in the ISA of this hipcc: the census in
+        // profiles/lstm_fwd_stage.md shows 2 moves per stage when it holds)
+        asm volatile("");
+        #pragma unroll
+        for (int m = 0; m < MT; ++m)
+          #pragma unroll
+          for (int q = 0; q < 4; ++q) acc[m][q] = zero4;
       }
-      // input term: previous layer's h from GLOBAL (L2-hot: this block wrote
-      // the same tile last layer); dense layer 0 reads x directly. The
-      // fragments were prefetched last stage; reload for t+1 right away.
-      if (!CIN1 || layer > 0) {
+      // input term: the fragments were prefetched last stage; reload for t+1
+      // right away
+      if constexpr (!SCALAR) {
         #pragma unroll
         for (int m = 0; m < MT; ++m)
           #pragma unroll
@@ -235,52 +273,78 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
         if (t + 1 < Tst) load_input(t + 1);
       }
 
-      // pointwise cell update in fragment layout (+ scalar-input term)
+      // pointwise cell update in fragment layout (+ the scalar-input term).
+      // Every rounding is pinned (stm_fmul / stm_fadd / fmaf): the results are
+      // those of the form this kernel had when its arithmetic was left to the
+      // compiler's FMA contraction. That fused the product of the GRU's n,
+      // one product of its h (z h_prev in the f16 scalar-input instantiation,
+      // (1-z) n in the others) and, in the dense-input instantiations only,
+      // f c of the LSTM's c; the scalar-input term was never fused.
+      constexpr bool GRU_FUSED_ZH = CIN1 && std::is_same<T, __half>::value;
       T hval[MT][4];     // [m][reg] this lane's h outputs (ch = hch)
-      T gsave[MT][16];   // [m][i f g o | r z n Bn][reg] post-activation gates
-      float csave[MT][4];  // [m][reg] training save (LSTM c_t / GRU h_{t-1})
+      // training saves, rounded element by element into the vectors their
+      // stores send (two values per v_cvt_pk, no packing arithmetic):
+      // gsave[m] = [i f | g o] (GRU: [r z | n Bn]) x [reg] post-activation
+      // gates, csave[m] = [reg] LSTM c_t / GRU h_{t-1}
+      frag gsave[MT][2];
+      elem4 csave[MT];
       #pragma unroll
       for (int m = 0; m < MT; ++m) {
         float xv[4];
-        if (CIN1 && layer == 0)
+        if constexpr (SCALAR) {
           #pragma unroll
           for (int r = 0; r < 4; ++r)
             xv[r] = toF<T>(((const T*)xbuf)[t * SEQ_TILE + 16 * m + 4 * lgrp + r]);
+        }
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float gi = acc[m][0][r] + bias[0];
-          float gf = acc[m][1][r] + bias[1];
-          float gg = acc[m][2][r] + bias[2];
-          float go = acc[m][3][r] + bias[3];
-          if (CIN1 && layer == 0) {
-            gi += xv[r] * wih0[0]; gf += xv[r] * wih0[1];
-            gg += xv[r] * wih0[2]; go += xv[r] * wih0[3];
+          float pre[4];
+          #pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            pre[q] = stm_fadd(acc[m][q][r], bias[q]);
+            if constexpr (SCALAR) pre[q] = stm_fadd(pre[q], stm_fmul(xv[r], wih0[q]));
           }
-          if (GRU) {
+          const float gi = pre[0], gf = pre[1], gg = pre[2], go = pre[3];
+          if constexpr (GRU) {
             // q-slots: gi = r-pre, gf = z-pre, gg = n_input, go = n_hidden
             const float r_ = stm_sigmoid(gi), z_ = stm_sigmoid(gf);
-            const float n_ = stm_tanh(gg + r_ * go);
+            const float n_ = stm_tanh(fmaf(r_, go, gg));
             const float hprev = c_state[m][r];
-            csave[m][r] = hprev;                        // bwd needs h_{t-1}
-            const float h_ = (1.f - z_) * n_ + z_ * hprev;
+            csave[m][r] = (elem)hprev;                  // bwd needs h_{t-1}
+            const float zn = stm_fmul(1.f - z_, n_);     // GRU_FUSED_ZH only
+            const float h_ = GRU_FUSED_ZH ? fmaf(z_, hprev, zn)
+                                          : fmaf(1.f - z_, n_, stm_fmul(z_, hprev));
             c_state[m][r] = h_;
-            hval[m][r] = fromF<T>(h_);
-            gsave[m][0 * 4 + r] = fromF<T>(r_);
-            gsave[m][1 * 4 + r] = fromF<T>(z_);
-            gsave[m][2 * 4 + r] = fromF<T>(n_);
-            gsave[m][3 * 4 + r] = fromF<T>(go);          // Bn = Un h + bhn
+            if constexpr (GRU_FUSED_ZH) {
+              // ... and that instantiation rounded the f16 h straight from the
+              // fused sum, not from its fp32 value. (GRU_FUSED_ZH and this asm
+              // only keep old bits: both can go with the first change that is
+              // allowed to move them.)
+              unsigned hw;
+              asm("v_fma_mixlo_f16 %0, %1, %2, %3"
+                  : "=v"(hw) : "v"(hprev), "v"(z_), "v"(zn));
+              hval[m][r] = __builtin_bit_cast(T, (unsigned short)hw);
+            } else {
+              hval[m][r] = fromF<T>(h_);
+            }
+            gsave[m][0][0 + r] = (elem)r_;
+            gsave[m][0][4 + r] = (elem)z_;
+            gsave[m][1][0 + r] = (elem)n_;
+            gsave[m][1][4 + r] = (elem)go;   // Bn = Un h + bhn
           } else {
             const float i_ = stm_sigmoid(gi), f_ = stm_sigmoid(gf);
             const float g_ = stm_tanh(gg), o_ = stm_sigmoid(go);
-            const float c_ = f_ * c_state[m][r] + i_ * g_;
+            const float ig = stm_fmul(i_, g_);
+            const float c_ = CIN1 ? stm_fadd(stm_fmul(f_, c_state[m][r]), ig)
+                                  : fmaf(f_, c_state[m][r], ig);
             c_state[m][r] = c_;
-            csave[m][r] = c_;
-            const float h_ = o_ * stm_tanh(c_);
+            csave[m][r] = (elem)c_;
+            const float h_ = stm_fmul(o_, stm_tanh(c_));
             hval[m][r] = fromF<T>(h_);
-            gsave[m][0 * 4 + r] = fromF<T>(i_);
-            gsave[m][1 * 4 + r] = fromF<T>(f_);
-            gsave[m][2 * 4 + r] = fromF<T>(g_);
-            gsave[m][3 * 4 + r] = fromF<T>(o_);
+            gsave[m][0][0 + r] = (elem)i_;
+            gsave[m][0][4 + r] = (elem)f_;
+            gsave[m][1][0 + r] = (elem)g_;
+            gsave[m][1][4 + r] = (elem)o_;
           }
         }
       }
@@ -302,15 +366,16 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
       // hand the slot off to global (next layer's input + wgrad/out source;
       // the last layer's sequence is dead in eval — only `out` is written)
       {
-        T* hp = hseq_g + ((long)layer * Tst + t) * (S_pad * RNN_H)
-                + (long)s0 * RNN_H;
-        const bool keep_h = (layer < L - 1) || (gates_g != nullptr);
-        char* slot = hslot(t);
-        for (int i = threadIdx.x; i < SEQ_TILE * 8; i += 256) {
-          const int c8 = i & 7, sr = i >> 3;
-          frag v = *(frag*)&slot[lds_swz(sr, c8 * 16)];
-          if (keep_h) *(frag*)&hp[sr * RNN_H + c8 * 8] = v;
-          if (layer == L - 1 && s0 + sr < S) {
+        static_assert(SEQ_TILE * 8 == 256, "one 16 B piece of the slot per thread");
+        const int c8 = threadIdx.x & 7, sr = threadIdx.x >> 3;
+        const frag v = *(const frag*)&hslot(t)[lds_swz(sr, c8 * 16)];
+        if constexpr (KEEP_H) {
+          char* hp = (char*)(hseq_g + ((long)layer * Tst + t) * (S_pad * RNN_H)
+                             + (long)s0 * RNN_H);
+          *(frag*)(hp + threadIdx.x * 16) = v;
+        }
+        if constexpr (TOP) {
+          if (s0 + sr < S) {
             if (ret_seq)
               *(frag*)&out[((long)(s0 + sr) * Tst + t) * RNN_H + c8 * 8] = v;
             else if (t == Tst - 1)
@@ -320,30 +385,36 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
       }
 
       // training saves: gates + cell, fragment-native (16B contiguous/lane)
-      if (gates_g) {
+      if constexpr (TRAIN) {
         const long base = ((long)layer * Tst + t);
         // gates: (L,Tst, S_pad*4H) as [wave][m][lane][16] T
-        T* gp = gates_g + base * (S_pad * 4 * RNN_H)
-                + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H)
-                + ((wv * MT) * 64) * 16;
+        char* gp = (char*)(gates_g + base * (S_pad * 4 * RNN_H)
+                           + (long)blockIdx.x * (SEQ_TILE * 4 * RNN_H));
         #pragma unroll
         for (int m = 0; m < MT; ++m)
-          *(((frag*)(gp + (m * 64 + lane) * 16)) + 0) = *(frag*)&gsave[m][0],
-          *(((frag*)(gp + (m * 64 + lane) * 16)) + 1) = *(frag*)&gsave[m][8];
+          #pragma unroll
+          for (int hq = 0; hq < 2; ++hq)
+            *(frag*)(gp + (savelane * 16 + (m * 64 * 16 + hq * 8) * sizeof(T))) = gsave[m][hq];
         // cell: (L,Tst, S_pad*H) model-dtype as [wave][m][lane][4]
         // (LSTM: c_t; GRU: h_{t-1}) — T-typed save halves HBM traffic vs
         // fp32; bwd tolerances cover the rounding (tests at 8% rel)
-        T* cp = cseq_g + base * (S_pad * RNN_H)
-                + (long)blockIdx.x * (SEQ_TILE * RNN_H) + (wv * MT) * 64 * 4;
+        char* cp = (char*)(cseq_g + base * (S_pad * RNN_H)
+                           + (long)blockIdx.x * (SEQ_TILE * RNN_H));
         #pragma unroll
-        for (int m = 0; m < MT; ++m) {
-          T c4[4];
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) c4[r] = fromF<T>(csave[m][r]);
-          *(ulong1*)(cp + (m * 64 + lane) * 4) = *(ulong1*)c4;
-        }
+        for (int m = 0; m < MT; ++m)
+          *(elem4*)(cp + (savelane * 4 + m * 64 * 4 * sizeof(T))) = csave[m];
       }
     }
+  };
+
+  for (int layer = 0; layer < L; ++layer) {
+    rnn_uniform_bool(layer == 0, [&](auto first_c) {
+      rnn_uniform_bool(gates_g != nullptr, [&](auto train_c) {
+        rnn_uniform_bool(layer == L - 1, [&](auto top_c) {
+          layer_body(layer, first_c, train_c, top_c);
+        });
+      });
+    });
     // layer boundary: the hseq_g stores must be visible to this block's
     // next-layer input loads (workgroup-scope fence + barrier)
     __threadfence_block();
@@ -429,13 +500,6 @@ extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
 //   dx / dh_g stores
 //   stage-in           the one wait for the saves; the stores stay in flight
 //   barrier            the next pointwise phase may overwrite the dA tile
-
-// f(std::true_type{}) or f(std::false_type{}) for a workgroup-uniform flag:
-// the device-side twin of stm_dispatch_bool
-template <typename F> __device__ __forceinline__ void rnn_uniform_bool(bool flag, F&& f) {
-  if (flag) f(std::true_type{});
-  else f(std::false_type{});
-}
 
 // four fp32 values rounded to T, as ONE 64-bit value (not four halves that
 // the compiler may keep in separate registers)
