@@ -14,6 +14,10 @@ model -> trainer -> test), plus MI355X extensions:
   --kernel-type / --K  graph-kernel family and order (override the preset);
                  dual_random_walk = bidirectional diffusion for directed graphs
   --directed     with --synthetic: asymmetric weighted random graphs
+  --horizon P    forecast steps t+1 .. t+P; output and targets (B, N, P, C)
+  --null-value V raw readings equal to V are missing: their targets become NaN
+                 and the masked loss and the masked test metrics skip them
+  --loss         MSE | MAE | Huber (overrides the preset)
 
 Distributed: launch under torchrun (one process per GPU, RCCL); rank/world
 are read from the environment and the train split is block-sharded.
@@ -64,6 +68,14 @@ def main():
                    help="polynomial / diffusion order (overrides the preset)")
     p.add_argument("--directed", action="store_true",
                    help="synthetic data: asymmetric weighted random graphs")
+    p.add_argument("--horizon", type=int, default=None,
+                   help="forecast horizon P >= 1 (steps ahead)")
+    p.add_argument("--null-value", type=float, default=None,
+                   help="raw reading that marks a missing value; selects the "
+                        "masked loss")
+    p.add_argument("--loss", type=str, default=None,
+                   choices=["MSE", "MAE", "Huber"],
+                   help="training loss (overrides the preset)")
     p.add_argument("--model-dir", type=str, default="./output")
     p.add_argument("--metrics", type=str, default=None, help="JSONL metrics path")
     p.add_argument("--graph", action="store_true",
@@ -85,6 +97,12 @@ def main():
         cfg = cfg.replace(kernel_type=args.kernel_type)
     if args.K is not None:
         cfg = cfg.replace(cheby_K=args.K)
+    if args.horizon is not None:
+        cfg = cfg.replace(horizon=args.horizon)
+    if args.null_value is not None:
+        cfg = cfg.replace(null_value=args.null_value)
+    if args.loss is not None:
+        cfg = cfg.replace(loss=args.loss)
     if args.obs_len != [3, 1, 1] or args.preset == "reference":
         cfg = cfg.replace(obs_len=list(args.obs_len), seq_len=sum(args.obs_len))
 
@@ -102,7 +120,8 @@ def main():
         dtype = torch.float32  # CPU oracle path runs fp32
 
     # ---- data (L1) ----
-    data_in = DataInput(M_adj=cfg.m_graphs, data_dir=args.data, norm_opt=True)
+    data_in = DataInput(M_adj=cfg.m_graphs, data_dir=args.data, norm_opt=True,
+                        null_value=cfg.null_value)
     if args.synthetic or not os.path.exists(args.data):
         raw = make_synthetic_dataset(n_nodes=cfg.n_nodes, m_graphs=cfg.m_graphs,
                                      directed=args.directed)
@@ -125,7 +144,8 @@ def main():
 
     # ---- loaders ----
     gen = DataGenerator(dt=cfg.dt, obs_len=tuple(cfg.obs_len),
-                        train_test_dates=args.dates, val_ratio=0.2)
+                        train_test_dates=args.dates, val_ratio=0.2,
+                        horizon=cfg.horizon)
     loaders = gen.get_data_loader(data, cfg.batch_size, device, rank=rank,
                                   world_size=world, shuffle_train=cfg.shuffle,
                                   dtype=dtype)
@@ -139,7 +159,12 @@ def main():
     hip_path = (device.type == "cuda" and _ops.hip_available()
                 and dtype in (torch.bfloat16, torch.float16)
                 and os.environ.get("STMGCN_IMPL", "hip") == "hip")
-    if hip_path and cfg.loss == "MSE":
+    if cfg.null_value is not None:
+        # targets carry NaN at missing readings: the masked loss (fused on the
+        # HIP path for all three kinds, the oracle elsewhere)
+        import functools
+        loss = functools.partial(_ops.masked_loss, kind=cfg.loss.lower())
+    elif hip_path and cfg.loss == "MSE":
         from stmgcn_amd.ops import mse_loss as loss
     else:
         loss = {"MSE": nn.MSELoss(), "MAE": nn.L1Loss(), "Huber": nn.SmoothL1Loss()}[cfg.loss]
@@ -166,6 +191,12 @@ def main():
         trainer.test(data_loader=loaders, sta_adj_list=sta_adj_list,
                      modes=["train", "test"], model_dir=args.model_dir,
                      data_class=data_in)
+        if hip_path:
+            # as bench.py reports it: an op that fell back to torch (only
+            # possible with STMGCN_ALLOW_FALLBACK=1) shows in the impl name
+            from stmgcn_amd.ops import hip_ops
+            n_fb = hip_ops.fallback_count()
+            print("impl:", "hip+fallback" if n_fb else "hip", "fallbacks:", n_fb)
     cleanup_distributed()
 
 

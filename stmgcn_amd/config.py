@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import dataclasses
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 
 @dataclass
@@ -29,6 +29,9 @@ class STMGCNConfig:
     n_blocks: int = 1                # stacked ST-MGCN blocks (deep variant = 4)
     gconv_use_bias: bool = True
     gconv_activation: str = "relu"
+    # forecast steps t+1 .. t+horizon; the head is nn.Linear(G, horizon *
+    # input_dim), column o = p*C + c, and the output (B, N, P, C) for P > 1
+    horizon: int = 1
 
     # --- numerics ---
     dtype: str = "fp32"              # fp32 | bf16 | fp16 (compute dtype on GPU)
@@ -49,6 +52,9 @@ class STMGCNConfig:
     # --- data windowing (reference Main.py:30-33, Data_Container.py:125-146) ---
     obs_len: List[int] = field(default_factory=lambda: [3, 1, 1])  # serial, daily, weekly
     dt: int = 1                      # hours per timestep
+    # raw readings equal to this value are missing: their targets become NaN
+    # and the masked loss / masked metrics skip them (None: nothing is masked)
+    null_value: Optional[float] = None
 
     # --- parallelism ---
     dp_degree: int = 1

@@ -903,6 +903,133 @@ at::Tensor mse_bwd(at::Tensor diff, at::Tensor gscale) {
   return dpred;
 }
 
+// ---- wide head (multi-step horizon): O = fc_weight.size(0), 2 <= O <= 32 ----
+static void head_multi_check(const at::Tensor& a, int64_t G, int64_t O) {
+  TORCH_CHECK(a.is_cuda() && (a.scalar_type() == at::kBFloat16 ||
+                              a.scalar_type() == at::kHalf),
+              "wide head serves bf16/f16");
+  TORCH_CHECK(O >= 2 && O <= 32 && G >= 8 && G <= 64 && G % 8 == 0,
+              "wide head serves 2 <= O <= 32, G <= 64 with G % 8 == 0");
+}
+
+// {y (B, N, O), fsum (B, N, G)}
+std::vector<at::Tensor> head_multi_fwd(std::vector<at::Tensor> feats,
+                                       at::Tensor w, at::Tensor bias) {
+  TORCH_CHECK(feats.size() >= 1 && feats.size() <= 3 && w.dim() == 2);
+  auto f0 = feats[0].contiguous();
+  TORCH_CHECK(f0.dim() == 3);
+  const long BN = (long)f0.size(0) * f0.size(1);
+  const int G = f0.size(2), O = w.size(0);
+  head_multi_check(f0, G, O);
+  TORCH_CHECK(w.size(1) == G && bias.numel() == O &&
+              w.scalar_type() == f0.scalar_type() &&
+              bias.scalar_type() == f0.scalar_type() && w.is_cuda() &&
+              bias.is_cuda());
+  std::vector<at::Tensor> fc{f0};
+  for (size_t m = 1; m < feats.size(); ++m) {
+    TORCH_CHECK(feats[m].sizes() == f0.sizes() && feats[m].is_cuda() &&
+                feats[m].scalar_type() == f0.scalar_type());
+    fc.push_back(feats[m].contiguous());
+  }
+  auto wc = w.contiguous(), bc = bias.contiguous();
+  auto y = at::empty({f0.size(0), f0.size(1), O}, f0.options());
+  auto fsum = at::empty_like(f0);
+  stmgcn_head_multi_fwd(stream(), dtype_code(f0), fc[0].data_ptr(),
+                        fc.size() > 1 ? fc[1].data_ptr() : nullptr,
+                        fc.size() > 2 ? fc[2].data_ptr() : nullptr,
+                        wc.data_ptr(), bc.data_ptr(), y.data_ptr(),
+                        fsum.data_ptr(), G, O, BN);
+  return {y, fsum};
+}
+
+at::Tensor head_multi_bwd(at::Tensor dy, at::Tensor w) {
+  TORCH_CHECK(dy.dim() == 3 && w.dim() == 2 && w.is_cuda());
+  dy = dy.contiguous();
+  const long BN = (long)dy.size(0) * dy.size(1);
+  const int O = w.size(0), G = w.size(1);
+  head_multi_check(dy, G, O);
+  TORCH_CHECK(dy.size(2) == O && w.scalar_type() == dy.scalar_type());
+  auto wc = w.contiguous();
+  auto dfeat = at::empty({dy.size(0), dy.size(1), G}, dy.options());
+  stmgcn_head_multi_bwd(stream(), dtype_code(dy), dy.data_ptr(), wc.data_ptr(),
+                        dfeat.data_ptr(), G, O, BN);
+  return dfeat;
+}
+
+static long head_multi_wgrad_check(at::Tensor& dy, at::Tensor& fsum) {
+  TORCH_CHECK(dy.dim() == 3 && fsum.dim() == 3 && fsum.is_cuda() &&
+              dy.scalar_type() == fsum.scalar_type() &&
+              dy.size(0) == fsum.size(0) && dy.size(1) == fsum.size(1));
+  dy = dy.contiguous();
+  fsum = fsum.contiguous();
+  head_multi_check(dy, fsum.size(2), dy.size(2));
+  return (long)fsum.size(0) * fsum.size(1);
+}
+
+// dW (O, G) = dy^T fsum and db (O,) = colsum(dy) as fp32 sums
+std::vector<at::Tensor> head_multi_wgrad(at::Tensor dy, at::Tensor fsum) {
+  const long BN = head_multi_wgrad_check(dy, fsum);
+  const int G = fsum.size(2), O = dy.size(2);
+  auto fopt = dy.options().dtype(at::kFloat);
+  auto dw = at::zeros({O, G}, fopt);
+  auto db = at::zeros({O}, fopt);
+  stmgcn_head_multi_wgrad(stream(), dtype_code(dy), dy.data_ptr(),
+                          fsum.data_ptr(), dw.data_ptr<float>(),
+                          db.data_ptr<float>(), nullptr, nullptr, nullptr, G, O,
+                          BN);
+  return {dw, db};
+}
+
+// Finishing form: dW (O, G) and db (O,) in the dtype of dy from one zero-filled
+// fp32 workspace (O*G sums, 32 db slots, ticket); the last workgroup rounds.
+std::vector<at::Tensor> head_multi_wgrad_grads(at::Tensor dy, at::Tensor fsum) {
+  const long BN = head_multi_wgrad_check(dy, fsum);
+  const int G = fsum.size(2), O = dy.size(2);
+  auto ws = at::zeros({(long)O * G + 32 + 8}, dy.options().dtype(at::kFloat));
+  float* wp = ws.data_ptr<float>();
+  auto dw = at::empty({O, G}, dy.options());
+  auto db = at::empty({O}, dy.options());
+  stmgcn_head_multi_wgrad(stream(), dtype_code(dy), dy.data_ptr(),
+                          fsum.data_ptr(), wp, wp + (long)O * G,
+                          (unsigned*)(wp + (long)O * G + 32), dw.data_ptr(),
+                          db.data_ptr(), G, O, BN);
+  return {dw, db};
+}
+
+// ---- masked loss: {res (2,) fp32 = loss, 1 / max(count_valid, 1); diff} ----
+std::vector<at::Tensor> masked_loss_fwd(at::Tensor pred, at::Tensor tgt,
+                                        int64_t kind) {
+  TORCH_CHECK(pred.is_cuda() && tgt.is_cuda() && pred.sizes() == tgt.sizes() &&
+              pred.scalar_type() == tgt.scalar_type());
+  TORCH_CHECK(kind >= 0 && kind <= 2, "masked loss kind: 0 mse, 1 mae, 2 huber");
+  // count_valid is a 32-bit integer sum
+  TORCH_CHECK(pred.numel() > 0 && pred.numel() < (1LL << 32));
+  pred = pred.contiguous();
+  tgt = tgt.contiguous();
+  auto fopt = pred.options().dtype(at::kFloat);
+  auto ws = at::zeros({4}, fopt);     // sum, count, ticket: one fill
+  auto res = at::empty({2}, fopt);
+  auto diff = at::empty_like(pred);
+  stmgcn_masked_loss_fwd(stream(), dtype_code(pred), (int)kind, pred.data_ptr(),
+                         tgt.data_ptr(), ws.data_ptr<float>(),
+                         res.data_ptr<float>(), diff.data_ptr(), pred.numel());
+  return {res, diff};
+}
+
+at::Tensor masked_loss_bwd(at::Tensor diff, at::Tensor res, at::Tensor gscale,
+                           int64_t kind) {
+  TORCH_CHECK(diff.is_cuda() && diff.is_contiguous() && res.is_cuda() &&
+              gscale.is_cuda() && res.scalar_type() == at::kFloat &&
+              gscale.scalar_type() == at::kFloat && res.numel() == 2 &&
+              res.is_contiguous() && gscale.numel() == 1);
+  TORCH_CHECK(kind >= 0 && kind <= 2 && diff.numel() > 0);
+  auto dpred = at::empty_like(diff);
+  stmgcn_masked_loss_bwd(stream(), dtype_code(diff), (int)kind, diff.data_ptr(),
+                         res.data_ptr<float>(), gscale.data_ptr<float>(),
+                         dpred.data_ptr(), diff.numel());
+  return dpred;
+}
+
 // Pack per-param grads (or zeros for undefined) into the flat grad arena.
 // grads: list aligned with the arena layout; offsets/lens in elements.
 void gather_grads(std::vector<at::Tensor> grads, std::vector<int64_t> ofs,
@@ -965,6 +1092,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_fwd", &head_fwd, "K7: branch-sum + FC head forward");
   m.def("head_bwd", &head_bwd, "K7: head backward (dfeat)");
   m.def("head_wgrad", &head_wgrad, "K7: dw/db reduction (no library GEMM)");
+  m.def("head_multi_fwd", &head_multi_fwd,
+        "K7 wide: branch-sum + FC head forward, 2 <= O <= 32 columns (MFMA)");
+  m.def("head_multi_bwd", &head_multi_bwd, "K7 wide: dfeat = dy W (MFMA)");
+  m.def("head_multi_wgrad", &head_multi_wgrad,
+        "K7 wide: dW / db reduction, fp32 sums");
+  m.def("head_multi_wgrad_grads", &head_multi_wgrad_grads,
+        "K7 wide: dW / db reduction finished in-kernel (parameter dtype)");
+  m.def("masked_loss_fwd", &masked_loss_fwd,
+        "K8 masked: MSE / MAE / Huber over non-NaN targets, loss on the device");
+  m.def("masked_loss_bwd", &masked_loss_bwd, "K8 masked: fused grad");
   m.def("mse_fwd", &mse_fwd, "K8: fused MSE loss forward");
   m.def("mse_bwd", &mse_bwd, "K8: fused MSE grad");
   m.def("adam_step", &adam_step, "K9: multi-tensor Adam over flat arena");

@@ -130,6 +130,22 @@ void stmgcn_head_wgrad(void* stream, int dtype, const void* dy, const void* fsum
     float* dw, float* db, int G, long BN);
 void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy, const void* fsum,
     float* dw, float* db, unsigned* ticket, void* dw_out, void* db_out, int G, long BN);
+// wide head: O = horizon * C output columns, 2 <= O <= 32, G <= 64 with
+// G % 8 == 0, bf16/f16. wgrad: ticket == null leaves the fp32 sums in dw / db
+void stmgcn_head_multi_fwd(void* stream, int dtype, const void* f0, const void* f1,
+    const void* f2, const void* w, const void* bias, void* y, void* fsum, int G, int O,
+    long BN);
+void stmgcn_head_multi_bwd(void* stream, int dtype, const void* dy, const void* w,
+    void* dfeat, int G, int O, long BN);
+void stmgcn_head_multi_wgrad(void* stream, int dtype, const void* dy, const void* fsum,
+    float* dw, float* db, unsigned* ticket, void* dw_out, void* db_out, int G, int O,
+    long BN);
+// masked loss (NaN target = missing): kind 0 mse, 1 mae, 2 huber; ws = 3 zeroed
+// words (sum, count, ticket), res = {loss, 1 / max(count_valid, 1)}
+void stmgcn_masked_loss_fwd(void* stream, int dtype, int kind, const void* pred,
+    const void* tgt, float* ws, float* res, void* diff, long n);
+void stmgcn_masked_loss_bwd(void* stream, int dtype, int kind, const void* diff,
+    const float* res, const float* gscale, void* dpred, long n);
 // dz = dy * (y > 0), bf16/f16
 void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y, void* dz,
     long n);

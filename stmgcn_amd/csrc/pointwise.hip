@@ -8,7 +8,10 @@
 //      workgroup per batch row runs the FC stages + one broadcast-multiply;
 //      backward mirrors it and also sums dw/db over the batch.
 //  K7  branch-fuse + FC head: y = (sum_m feats_m) @ W^T + b (STMGCN.py:116-118)
+//      head_multi_*: the same head with 2..32 output columns (multi-step
+//      horizon, column o = p*C + c) on MFMA tiles
 //  K8  fused MSE loss + grad  (Model_Trainer.py:38)
+//      masked_loss_*: MSE / MAE / Huber over the targets that are not NaN
 //  K9  multi-tensor Adam over a flat fp32 master arena with bf16/f16 working
 //      params (torch.optim.Adam semantics incl. L2-style weight decay)
 
@@ -370,6 +373,221 @@ __global__ void head_wgrad_kernel(const T* __restrict__ dy,
   }
 }
 
+// ---- K7 wide: head with O = P*C output columns, 2 <= O <= 32 --------------
+// (multi-step horizon; column o = p*C + c). G <= 64 with G % 8 == 0, so a
+// lane's 8 channels are all inside or all outside a row and every 16-byte
+// access is aligned. The MFMA lane maps are those of mfma_probe_kernel.
+#define HEADM_MAX_O 32
+
+// 8 elements of T as one MFMA operand and as one 16-byte word
+template <typename T> union HeadFrag {
+  uint4 u;
+  T t[8];
+  typename Frag8<T>::type v;
+  __device__ HeadFrag() : u(make_uint4(0u, 0u, 0u, 0u)) {}
+};
+
+// y (BN, O) = fsum (BN, G) . W^T + b with fsum = sum_m f_m rounded once to T
+// and stored for the backward. One wave per 16 rows, four waves a workgroup.
+// A = fsum tile, built in registers from the branch loads (lane: row l % 16,
+// channels 32 s + 8 (l / 16) .. + 8 of K-step s; zero for row >= BN or
+// channel >= G); B[k][n] = W[n][k], held for the whole kernel (NCT column
+// tiles x 2 K-steps, zero for column >= O or channel >= G).
+template <typename T, int NCT>
+__global__ void head_multi_fwd_kernel(const T* __restrict__ f0,
+                                      const T* __restrict__ f1,
+                                      const T* __restrict__ f2,
+                                      const T* __restrict__ w,      // (O, G)
+                                      const T* __restrict__ bias_p, // (O,)
+                                      T* __restrict__ y,            // (BN, O)
+                                      T* __restrict__ fsum,         // (BN, G)
+                                      int G, int O, long BN) {
+  const int lane = threadIdx.x & 63;
+  const int l16 = lane & 15, lgrp = lane >> 4;
+  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+  if (row0 >= BN) return;          // wave-uniform; the kernel has no barrier
+  HeadFrag<T> bw[NCT][2];
+  #pragma unroll
+  for (int ct = 0; ct < NCT; ++ct)
+    #pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int o = ct * 16 + l16, k0 = s * 32 + lgrp * 8;
+      if (o < O && k0 < G) bw[ct][s].u = *(const uint4*)&w[(long)o * G + k0];
+    }
+  const long row = row0 + l16;
+  f32x4 acc[NCT];
+  #pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+  #pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const int k0 = s * 32 + lgrp * 8;
+    HeadFrag<T> a;
+    if (row < BN && k0 < G) {
+      const long at = row * G + k0;
+      HeadFrag<T> x0, x1, x2;
+      x0.u = *(const uint4*)&f0[at];
+      if (f1) x1.u = *(const uint4*)&f1[at];
+      if (f2) x2.u = *(const uint4*)&f2[at];
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = toF<T>(x0.t[j]);
+        if (f1) v += toF<T>(x1.t[j]);
+        if (f2) v += toF<T>(x2.t[j]);
+        a.t[j] = fromF<T>(v);
+      }
+      *(uint4*)&fsum[at] = a.u;
+    }
+    #pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+      acc[ct] = mfma16x16x32(a.v, bw[ct][s].v, acc[ct]);
+  }
+  // D: lane holds rows 4 (l / 16) + r of column l % 16 of each column tile
+  #pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    const int o = ct * 16 + l16;
+    if (o >= O) continue;
+    const float bv = toF<T>(bias_p[o]);
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long rr = row0 + lgrp * 4 + r;
+      if (rr < BN) y[rr * O + o] = fromF<T>(acc[ct][r] + bv);
+    }
+  }
+}
+
+// dfeat (BN, G) = dY (BN, O) . W (O, G), the same for every branch. Computed
+// transposed, D'[g][row] = sum_o W[o][g] dY[row][o], so that a lane's four
+// accumulators are four consecutive channels of one row: one 8-byte store.
+// The reduction index o is padded with zeros to the one K-step of 32. A row
+// of dY is O contiguous elements and O need not be a multiple of 8, so both
+// operands are guarded element loads: nothing past a row's end is read.
+template <typename T>
+__global__ void head_multi_bwd_kernel(const T* __restrict__ dy,  // (BN, O)
+                                      const T* __restrict__ w,   // (O, G)
+                                      T* __restrict__ dfeat,     // (BN, G)
+                                      int G, int O, long BN) {
+  const int lane = threadIdx.x & 63;
+  const int l16 = lane & 15, lgrp = lane >> 4;
+  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+  if (row0 >= BN) return;          // wave-uniform; the kernel has no barrier
+  const long row = row0 + l16;
+  HeadFrag<T> b;                   // B'[k = o][n = row] = dY[row][o]
+  if (row < BN) {
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int o = lgrp * 8 + j;
+      if (o < O) b.t[j] = dy[row * O + o];
+    }
+  }
+  for (int gt = 0; gt * 16 < G; ++gt) {
+    HeadFrag<T> a;                 // A'[m = g][k = o] = W[o][g]
+    const int g = gt * 16 + l16;
+    if (g < G) {
+      #pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int o = lgrp * 8 + j;
+        if (o < O) a.t[j] = w[(long)o * G + g];
+      }
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = mfma16x16x32(a.v, b.v, acc);
+    // D': lane holds channels gt*16 + 4 (l / 16) + r of row l % 16
+    const int g0 = gt * 16 + lgrp * 4;
+    if (row < BN && g0 < G)
+      stm_store4<T>(&dfeat[row * G + g0], acc[0], acc[1], acc[2], acc[3]);
+  }
+}
+
+// dW (O, G) = dY^T . fsum, db (O,) = colsum(dY): head_wgrad_kernel with up to
+// 8 output columns per thread. Wave wv serves column group og = wv % NG (NG =
+// ceil(O / 8) groups of 8 columns) and, where NG < 4, every (4 / NG)-th row of
+// the workgroup's chunk; lane g owns channel g. The dY values are wave-uniform
+// scalar loads; two row chains are in flight. The waves of a column group meet
+// in LDS, and one atomic per (o, g) and workgroup goes to the fp32 sums.
+// FIN: as in head_wgrad_kernel, the last workgroup to arrive writes dW / db in
+// the parameter dtype (the ticket sits in the same zeroed workspace).
+template <typename T, bool FIN>
+__global__ void head_multi_wgrad_kernel(const T* __restrict__ dy,    // (BN, O)
+                                        const T* __restrict__ fsum,  // (BN, G)
+                                        float* __restrict__ dw,  // (O*G) zeroed
+                                        float* __restrict__ db,  // (O,) zeroed
+                                        int G, int O, long BN, unsigned* ticket,
+                                        T* __restrict__ dw_out,
+                                        T* __restrict__ db_out) {
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  const int NG = (O + 7) >> 3;            // 1..4
+  const int WPG = 4 / NG;                 // waves per column group: 4, 2, 1, 1
+  const int og = wv % NG, sub = wv / NG;
+  const bool active = sub < WPG;          // NG == 3 leaves wave 3 idle
+  const int o0 = og * 8;
+  const int no = min(8, O - o0);
+  const long chunk = (BN + gridDim.x - 1) / gridDim.x;
+  const long r0 = (long)blockIdx.x * chunk;
+  const long r1 = (r0 + chunk < BN) ? r0 + chunk : BN;
+  float acc[8], acc2[8], accb[8];
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = acc2[j] = accb[j] = 0.f;
+  if (active) {
+    const bool in = lane < G;
+    long r = r0 + sub;
+    for (; r + WPG < r1; r += 2 * WPG) {
+      const float f = in ? toF<T>(fsum[r * G + lane]) : 0.f;
+      const float f2 = in ? toF<T>(fsum[(r + WPG) * G + lane]) : 0.f;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < no) {
+          const float d = toF<T>(dy[r * O + o0 + j]);
+          const float d2 = toF<T>(dy[(r + WPG) * O + o0 + j]);
+          acc[j] += d * f;
+          acc2[j] += d2 * f2;
+          accb[j] += d + d2;
+        }
+    }
+    for (; r < r1; r += WPG) {
+      const float f = in ? toF<T>(fsum[r * G + lane]) : 0.f;
+      #pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < no) {
+          const float d = toF<T>(dy[r * O + o0 + j]);
+          acc[j] += d * f;
+          accb[j] += d;
+        }
+    }
+  }
+  __shared__ float red[4][9][64];         // [wave][8 columns + db][lane]
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) red[wv][j][lane] = acc[j] + acc2[j];
+  // db: lane j of the wave carries column j's sum (every lane has them all)
+  {
+    float bsel = 0.f;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) bsel = (lane == j) ? accb[j] : bsel;
+    red[wv][8][lane] = bsel;
+  }
+  __syncthreads();
+  if (wv < NG) {                          // wave og gathers its group's waves
+    #pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      float v = 0.f;
+      for (int s = 0; s < WPG; ++s) v += red[wv + s * NG][j][lane];
+      if (j < 8) {
+        if (j < no && lane < G) unsafeAtomicAdd(&dw[(long)(o0 + j) * G + lane], v);
+      } else if (lane < no) {
+        unsafeAtomicAdd(&db[o0 + lane], v);
+      }
+    }
+  }
+  if constexpr (FIN) {
+    // the flag reuses red: its readers are behind the helper's first barrier
+    if (!stm_last_arriver(ticket, gridDim.x, (int*)&red[0][0][0])) return;
+    // O*G is a multiple of 8: four sums per thread, one 8-byte store each
+    for (int i = threadIdx.x * 4; i < O * G; i += 4 * blockDim.x)
+      stm_store4<T>(&dw_out[i], dw[i], dw[i + 1], dw[i + 2], dw[i + 3]);
+    if (threadIdx.x < O) db_out[threadIdx.x] = fromF<T>(db[threadIdx.x]);
+  }
+}
+
 // dz = dy * (y > 0): the ReLU mask of the graph-conv backward in one pass.
 // The product is formed in fp32 (dy * 1 and dy * 0 are exact), so the result,
 // the sign of a zero included, is what dy * (y > 0).to(dtype) gives.
@@ -422,6 +640,102 @@ __global__ void mse_bwd_kernel(const T* __restrict__ diff,
                                T* __restrict__ dpred, float two_over_n, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dpred[i] = fromF<T>(toF<T>(diff[i]) * two_over_n * gscale[0]);
+}
+
+// ---- K8 masked: MSE / MAE / Huber over the valid targets -------------------
+// A missing target is NaN (valid = target == target). loss = sum_valid l(d) /
+// max(count_valid, 1), d = pred - target; kind 0: d^2, 1: |d|, 2: Huber with
+// delta = 1 (SmoothL1Loss). One pass stores diff (0 on masked elements) and
+// reduces sum l(d) and count_valid; the last workgroup to arrive writes the
+// loss and 1 / max(count, 1) to device memory, so the host reads nothing and
+// the step stays capturable. The sum is fp32 (an f16 sum of 70001 terms would
+// overflow); count_valid is summed as a 32-bit unsigned integer, exact for
+// every numel below 2^32 (the binding checks that).
+#define MLOSS_PER_BLOCK 2048   // 8 elements per thread, 256 apart
+
+template <int KIND> __device__ __forceinline__ float mloss_value(float d) {
+  const float a = fabsf(d);
+  if (KIND == 0) return d * d;
+  if (KIND == 1) return a;
+  return a < 1.f ? 0.5f * d * d : a - 0.5f;
+}
+// l'(d), with sign(0) = 0 for MAE
+template <int KIND> __device__ __forceinline__ float mloss_grad(float d) {
+  const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+  if (KIND == 0) return 2.f * d;
+  if (KIND == 1) return sg;
+  return fabsf(d) < 1.f ? d : sg;
+}
+
+template <typename T, int KIND>
+__global__ void masked_loss_fwd_kernel(const T* __restrict__ pred,
+                                       const T* __restrict__ tgt,
+                                       float* sum,                  // zeroed
+                                       unsigned* count,             // zeroed
+                                       unsigned* ticket,            // zeroed
+                                       float* __restrict__ res,  // loss, 1/count
+                                       T* __restrict__ diff, long n) {
+  __shared__ float red[4];
+  __shared__ unsigned redc[4];
+  __shared__ int flag;
+  const long base = (long)blockIdx.x * MLOSS_PER_BLOCK + threadIdx.x;
+  float v = 0.f;
+  unsigned c = 0;
+  #pragma unroll
+  for (int k = 0; k < MLOSS_PER_BLOCK / 256; ++k) {
+    const long i = base + k * 256;
+    if (i < n) {
+      const float t = toF<T>(tgt[i]);
+      const bool valid = t == t;
+      const float d = valid ? toF<T>(pred[i]) - t : 0.f;
+      diff[i] = fromF<T>(d);
+      v += mloss_value<KIND>(d);
+      c += valid ? 1u : 0u;
+    }
+  }
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    v += __shfl_down(v, off, 64);
+    c += __shfl_down(c, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = v;
+    redc[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsafeAtomicAdd(sum, red[0] + red[1] + red[2] + red[3]);
+    atomicAdd(count, redc[0] + redc[1] + redc[2] + redc[3]);
+  }
+  if (!stm_last_arriver(ticket, gridDim.x, &flag)) return;
+  if (threadIdx.x == 0) {
+    const unsigned cv = *count;
+    const float inv = 1.f / (float)(cv > 0u ? cv : 1u);
+    res[0] = *sum * inv;
+    res[1] = inv;
+  }
+}
+
+// dpred = l'(diff) * inv_count * gscale. The mask is not saved and the target
+// is not read again: a masked element's stored diff is 0, and l'(0) = 0 for
+// all three kinds (sign(0) = 0), so its gradient is exactly 0.
+template <typename T, int KIND>
+__global__ void masked_loss_bwd_kernel(const T* __restrict__ diff,
+                                       const float* __restrict__ res,
+                                       const float* __restrict__ gscale,
+                                       T* __restrict__ dpred, long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    dpred[i] = fromF<T>(mloss_grad<KIND>(toF<T>(diff[i])) * (res[1] * gscale[0]));
+}
+
+// f(std::integral_constant<int, kind>{}) for kind 0 (mse), 1 (mae), 2 (huber)
+template <typename F> void mloss_dispatch_kind(int kind, F&& f) {
+  switch (kind) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+  }
 }
 
 // ---- K9: multi-tensor Adam over a flat arena ------------------------------
@@ -629,6 +943,88 @@ void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy,
                              int G, long BN) {
   head_wgrad_launch(stream, dtype, dy, fsum, dw, db, ticket, dw_out, db_out, G,
                     BN);
+}
+
+// wide head, 2 <= O <= 32, G <= 64 with G % 8 == 0 (bindings.cpp checks): one
+// wave per 16 rows, 64 rows per workgroup
+void stmgcn_head_multi_fwd(void* stream, int dtype, const void* f0,
+                           const void* f1, const void* f2, const void* w,
+                           const void* bias, void* y, void* fsum, int G, int O,
+                           long BN) {
+  if (BN <= 0) return;
+  const dim3 grid((unsigned)((BN + 63) / 64));
+  stm_dispatch_lowp("stmgcn_head_multi_fwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    stm_dispatch_bool(O > 16, [&](auto two) {
+      constexpr int NCT = decltype(two)::value ? 2 : 1;
+      hipLaunchKernelGGL((head_multi_fwd_kernel<T, NCT>), grid, dim3(256), 0,
+                         (hipStream_t)stream, (const T*)f0, (const T*)f1,
+                         (const T*)f2, (const T*)w, (const T*)bias, (T*)y,
+                         (T*)fsum, G, O, BN);
+    });
+  });
+}
+
+void stmgcn_head_multi_bwd(void* stream, int dtype, const void* dy,
+                           const void* w, void* dfeat, int G, int O, long BN) {
+  if (BN <= 0) return;
+  stm_dispatch_lowp("stmgcn_head_multi_bwd", dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(head_multi_bwd_kernel<T>,
+                       dim3((unsigned)((BN + 63) / 64)), dim3(256), 0,
+                       (hipStream_t)stream, (const T*)dy, (const T*)w,
+                       (T*)dfeat, G, O, BN);
+  });
+}
+
+// ticket == null: the accumulate-only form (fp32 sums left in dw (O*G) / db
+// (O)); otherwise the finishing form, dw_out (O, G) / db_out (O,) in `dtype`
+void stmgcn_head_multi_wgrad(void* stream, int dtype, const void* dy,
+                             const void* fsum, float* dw, float* db,
+                             unsigned* ticket, void* dw_out, void* db_out,
+                             int G, int O, long BN) {
+  long nblk = (BN + 255) / 256;   // as head_wgrad: 128 blocks at bench size
+  if (nblk > 512) nblk = 512;
+  if (nblk < 1) nblk = 1;
+  stm_dispatch_lowp("stmgcn_head_multi_wgrad", dtype, [&](auto t) {
+    using T = decltype(t);
+    stm_dispatch_bool(ticket != nullptr, [&](auto fin) {
+      hipLaunchKernelGGL((head_multi_wgrad_kernel<T, decltype(fin)::value>),
+                         dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
+                         (const T*)dy, (const T*)fsum, dw, db, G, O, BN, ticket,
+                         (T*)dw_out, (T*)db_out);
+    });
+  });
+}
+
+// ws: 3 zero-filled words (fp32 sum, unsigned count, ticket); res: loss and
+// 1 / max(count, 1); kind 0 mse, 1 mae, 2 huber
+void stmgcn_masked_loss_fwd(void* stream, int dtype, int kind, const void* pred,
+                            const void* tgt, float* ws, float* res, void* diff,
+                            long n) {
+  const dim3 grid((unsigned)((n + MLOSS_PER_BLOCK - 1) / MLOSS_PER_BLOCK));
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    mloss_dispatch_kind(kind, [&](auto k) {
+      hipLaunchKernelGGL((masked_loss_fwd_kernel<T, decltype(k)::value>), grid,
+                         dim3(256), 0, (hipStream_t)stream, (const T*)pred,
+                         (const T*)tgt, ws, (unsigned*)(ws + 1),
+                         (unsigned*)(ws + 2), res, (T*)diff, n);
+    });
+  });
+}
+
+void stmgcn_masked_loss_bwd(void* stream, int dtype, int kind, const void* diff,
+                            const float* res, const float* gscale, void* dpred,
+                            long n) {
+  stm_dispatch_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    mloss_dispatch_kind(kind, [&](auto k) {
+      hipLaunchKernelGGL((masked_loss_bwd_kernel<T, decltype(k)::value>),
+                         grid1d(n), dim3(256), 0, (hipStream_t)stream,
+                         (const T*)diff, res, gscale, (T*)dpred, n);
+    });
+  });
 }
 
 void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,

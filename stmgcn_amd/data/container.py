@@ -41,10 +41,15 @@ class DataInput:
 
     ADJ_KEYS = ["neighbor_adj", "trans_adj", "semantic_adj"]
 
-    def __init__(self, M_adj: int, data_dir: str, norm_opt: bool = True):
+    def __init__(self, M_adj: int, data_dir: str, norm_opt: bool = True,
+                 null_value: Optional[float] = None):
         self.M_sta = M_adj
         self.data_dir = data_dir
         self.norm_opt = norm_opt
+        # raw readings equal to null_value are missing (sensor outage): the
+        # loaders get a second series, "taxi_target", with NaN in their place,
+        # and take the targets y from it. The inputs x stay as loaded.
+        self.null_value = null_value
         self._min: Optional[float] = None
         self._max: Optional[float] = None
 
@@ -54,6 +59,7 @@ class DataInput:
         print("Available keys:", list(npz.keys()))
         dataset: Dict[str, np.ndarray] = {}
         dataset["taxi"] = self.minmax_normalize(npz["taxi"]) if self.norm_opt else npz["taxi"]
+        self._mark_missing(npz["taxi"], dataset)
         for k in range(self.M_sta):
             key = self.ADJ_KEYS[k]
             dataset[key] = npz[key]
@@ -64,7 +70,19 @@ class DataInput:
         out = dict(data)
         if self.norm_opt:
             out["taxi"] = self.minmax_normalize(out["taxi"])
+        self._mark_missing(data["taxi"], out)
         return out
+
+    def _mark_missing(self, raw: np.ndarray, dataset: Dict[str, np.ndarray]) -> None:
+        """NaN marking, decided on the raw readings (before normalisation):
+        dataset["taxi_target"] = the loaded series with NaN wherever raw ==
+        null_value. NaN survives the casts to bf16 / f16 and no real reading
+        rounds to it. Nothing is added without a null_value."""
+        if self.null_value is None:
+            return
+        tgt = np.array(dataset["taxi"], dtype=np.result_type(dataset["taxi"], np.float32))
+        tgt[raw == self.null_value] = np.nan
+        dataset["taxi_target"] = tgt
 
     def minmax_normalize(self, x: np.ndarray) -> np.ndarray:
         self._max, self._min = float(x.max()), float(x.min())
@@ -89,14 +107,22 @@ class DataInput:
 
 
 def sliding_windows(data: np.ndarray, serial_len: int, daily_len: int,
-                    weekly_len: int, day_timesteps: int):
+                    weekly_len: int, day_timesteps: int, horizon: int = 1,
+                    target: Optional[np.ndarray] = None):
     """Vectorized equivalent of the reference's get_feats + get_periodic_skip_seq
     (Data_Container.py:125-146). Returns (x_seq, y) where x_seq is the
     weekly|daily|serial concat (n_samples, T, N, C), oldest-first per component.
+
+    horizon = P > 1: anchors run start .. T_total - P and y is (S, N, P, C)
+    with y[s, n, p, c] = data[a_s + p, n, c] — the model's output layout, built
+    here once on the host. target: the array y is taken from where it differs
+    from data (the series with NaN at missing readings); x always reads data.
     """
+    if horizon < 1:
+        raise ValueError(f"horizon must be >= 1, got {horizon}")
     T_total = data.shape[0]
     start = max(serial_len, daily_len * day_timesteps, weekly_len * day_timesteps * 7)
-    anchors = np.arange(start, T_total)                       # one sample per anchor t
+    anchors = np.arange(start, T_total - horizon + 1)         # one sample per anchor t
     offsets: List[np.ndarray] = []
     if weekly_len > 0:
         p = weekly_len * day_timesteps * 7
@@ -110,7 +136,11 @@ def sliding_windows(data: np.ndarray, serial_len: int, daily_len: int,
     off = np.concatenate(offsets)                             # (T_win,)
     idx = anchors[:, None] + off[None, :]                     # (S, T_win)
     x_seq = data[idx]                                         # (S, T_win, N, C)
-    y = data[anchors]                                         # (S, N, C)
+    src = data if target is None else target
+    if horizon == 1:
+        return x_seq, src[anchors]                            # (S, N, C)
+    steps = anchors[:, None] + np.arange(horizon)[None, :]    # (S, P)
+    y = np.ascontiguousarray(np.moveaxis(src[steps], 1, 2))   # (S, N, P, C)
     return x_seq, y
 
 
@@ -195,7 +225,8 @@ class DataGenerator:
     """
 
     def __init__(self, dt: int, obs_len: Sequence[int], train_test_dates: List[str],
-                 val_ratio: float = 0.2, year: int = 2017):
+                 val_ratio: float = 0.2, year: int = 2017, horizon: int = 1):
+        self.horizon = horizon
         self.day_timesteps = 24 // dt
         self.serial_len, self.daily_len, self.weekly_len = obs_len
         self.train_test_dates = train_test_dates
@@ -220,15 +251,17 @@ class DataGenerator:
         # observable behavior at the defaults, well-defined for other dates.
         return 0, {"train": train_len, "validate": validate_len, "test": test_len}
 
-    def window(self, taxi: np.ndarray):
+    def window(self, taxi: np.ndarray, target: Optional[np.ndarray] = None):
         return sliding_windows(taxi, self.serial_len, self.daily_len,
-                               self.weekly_len, self.day_timesteps)
+                               self.weekly_len, self.day_timesteps,
+                               horizon=self.horizon, target=target)
 
     def get_data_loader(self, data: Dict[str, np.ndarray], batch_size: int,
                         device, rank: int = 0, world_size: int = 1,
                         shuffle_train: bool = False,
                         dtype: torch.dtype = torch.float32) -> Dict[str, DeviceLoader]:
-        x_seq, y = self.window(data["taxi"])
+        # targets come from the NaN-marked series when DataInput made one
+        x_seq, y = self.window(data["taxi"], data.get("taxi_target"))
         avail = x_seq.shape[0]
         need = sum(self.mode_len.values())
         if need > avail:

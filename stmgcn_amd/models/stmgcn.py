@@ -190,9 +190,13 @@ class ST_MGCN(nn.Module):
     def __init__(self, M: int, seq_len: int, n_nodes: int, input_dim: int,
                  lstm_hidden_dim: int, lstm_num_layers: int, gcn_hidden_dim: int,
                  sta_kernel_config: dict, gconv_use_bias: bool = True,
-                 gconv_activation: str = "relu", rnn_cell: str = "lstm"):
+                 gconv_activation: str = "relu", rnn_cell: str = "lstm",
+                 horizon: int = 1):
         super().__init__()
+        if horizon < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
         self.M = M
+        self.horizon = horizon
         self.n_nodes = n_nodes
         self.seq_len = seq_len
         self.input_dim = input_dim
@@ -207,7 +211,9 @@ class ST_MGCN(nn.Module):
             GCN(sta_K, lstm_hidden_dim, gcn_hidden_dim, bias=gconv_use_bias,
                 activation=gconv_activation)
             for _ in range(M)])
-        self.fc = nn.Linear(gcn_hidden_dim, input_dim)
+        # one head for all P = horizon steps: output column o = p*C + c
+        # (P = 1: the reference's nn.Linear(G, C), same state-dict keys)
+        self.fc = nn.Linear(gcn_hidden_dim, horizon * input_dim)
 
     @staticmethod
     def get_support_K(config: dict) -> int:
@@ -226,7 +232,9 @@ class ST_MGCN(nn.Module):
         raise ValueError(f"unknown kernel_type {kt!r}")
 
     def forward(self, obs_seq: torch.Tensor, sta_adj_list: Sequence[AdjLike]) -> torch.Tensor:
-        """obs_seq: (B, T, N, C); sta_adj_list: M supports -> (B, N, C).
+        """obs_seq: (B, T, N, C); sta_adj_list: M supports -> (B, N, C), or
+        (B, N, P, C) for horizon P > 1: each node's forecast of steps
+        t+1 .. t+P, a view of the head's (B, N, P*C) output.
 
         Branches are independent (reference runs them sequentially,
         STMGCN.py:112-115); on GPU the fused kernels batch the M dimension
@@ -253,7 +261,10 @@ class ST_MGCN(nn.Module):
             for m in range(self.M):
                 h = self.rnn_list[m](sta_adj_list[m], obs_seq)     # (B,N,H)
                 feat_list.append(self.gcn_list[m](sta_adj_list[m], h))  # (B,N,G)
-        return ops.branch_fuse_head(feat_list, self.fc.weight, self.fc.bias)  # K7
+        out = ops.branch_fuse_head(feat_list, self.fc.weight, self.fc.bias)  # K7
+        if self.horizon > 1:
+            out = out.view(out.shape[0], out.shape[1], self.horizon, self.input_dim)
+        return out
 
 
 class STMGCNBlock(nn.Module):
@@ -317,10 +328,14 @@ class StackedSTMGCN(nn.Module):
     def __init__(self, M: int, seq_len: int, n_nodes: int, input_dim: int,
                  lstm_hidden_dim: int, lstm_num_layers: int, gcn_hidden_dim: int,
                  sta_kernel_config: dict, n_blocks: int = 4, rnn_cell: str = "gru",
-                 gconv_use_bias: bool = True, gconv_activation: str = "relu"):
+                 gconv_use_bias: bool = True, gconv_activation: str = "relu",
+                 horizon: int = 1):
         super().__init__()
+        if horizon < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
         sta_K = ST_MGCN.get_support_K(sta_kernel_config)
         self.M, self.n_blocks = M, n_blocks
+        self.horizon, self.input_dim = horizon, input_dim
         dims = [input_dim] + [gcn_hidden_dim] * n_blocks
         self.blocks = nn.ModuleList([
             STMGCNBlock(M, seq_len, dims[i], lstm_hidden_dim, lstm_num_layers,
@@ -328,13 +343,16 @@ class StackedSTMGCN(nn.Module):
                         gconv_use_bias=gconv_use_bias,
                         gconv_activation=gconv_activation)
             for i in range(n_blocks)])
-        self.fc = nn.Linear(gcn_hidden_dim, input_dim)
+        self.fc = nn.Linear(gcn_hidden_dim, horizon * input_dim)  # o = p*C + c
 
     def forward(self, obs_seq: torch.Tensor, sta_adj_list: Sequence[AdjLike]) -> torch.Tensor:
         x = obs_seq
         for blk in self.blocks:
             x = blk(x, sta_adj_list)
-        return self.fc(x[:, -1])                     # (B, N, C)
+        out = self.fc(x[:, -1])                      # (B, N, P*C)
+        if self.horizon > 1:                         # (B, N, P, C)
+            out = out.view(out.shape[0], out.shape[1], self.horizon, self.input_dim)
+        return out
 
 
 def build_model(cfg) -> nn.Module:
@@ -346,8 +364,10 @@ def build_model(cfg) -> nn.Module:
                              cfg.gcn_hidden_dim, kconf, n_blocks=cfg.n_blocks,
                              rnn_cell=cfg.rnn_cell,
                              gconv_use_bias=cfg.gconv_use_bias,
-                             gconv_activation=cfg.gconv_activation)
+                             gconv_activation=cfg.gconv_activation,
+                             horizon=cfg.horizon)
     return ST_MGCN(cfg.m_graphs, cfg.seq_len, cfg.n_nodes, cfg.input_dim,
                    cfg.lstm_hidden_dim, cfg.lstm_num_layers, cfg.gcn_hidden_dim,
                    kconf, gconv_use_bias=cfg.gconv_use_bias,
-                   gconv_activation=cfg.gconv_activation, rnn_cell=cfg.rnn_cell)
+                   gconv_activation=cfg.gconv_activation, rnn_cell=cfg.rnn_cell,
+                   horizon=cfg.horizon)

@@ -131,10 +131,32 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.mse_loss(pred, target)
 
 
+def masked_loss(pred: torch.Tensor, target: torch.Tensor,
+                kind: str = "mse") -> torch.Tensor:
+    """Mean of l(pred - target) over the targets that are not NaN (a NaN
+    target marks a missing reading); kind = mse | mae | huber (delta = 1).
+    0 with a zero gradient when every target is masked. Fused loss + grad on
+    GPU (bf16 / f16 / fp32); the reference_impl oracle elsewhere."""
+    if kind not in ("mse", "mae", "huber"):
+        raise ValueError(f"unknown masked loss kind {kind!r}")
+    if target.shape != pred.shape:
+        raise ValueError(f"shape mismatch: pred {tuple(pred.shape)}, "
+                         f"target {tuple(target.shape)}")
+    if (pred.is_cuda and impl_mode() == "hip" and pred.dtype == target.dtype
+            and pred.dtype in (torch.bfloat16, torch.float16, torch.float32)):
+        from .hip_ops import MASKED_LOSS_KINDS, MaskedLossFn
+        return MaskedLossFn.apply(pred, target, MASKED_LOSS_KINDS[kind])
+    return ref.masked_loss(pred, target, kind)
+
+
 def branch_fuse_head(branch_feats: List[torch.Tensor], fc_weight: torch.Tensor,
                      fc_bias: torch.Tensor) -> torch.Tensor:
-    """Sum over M branches + FC head (reference STMGCN.py:116-118)."""
+    """Sum over M branches + FC head (reference STMGCN.py:116-118). Any
+    fc_weight.shape[0] = O; a multi-step model views the (B, N, O) result as
+    (B, N, P, C), column o = p*C + c."""
     if branch_feats[0].is_cuda and impl_mode() == "hip":
-        from .hip_ops import branch_fuse_head_hip
+        from .hip_ops import branch_fuse_head_hip, branch_fuse_head_multi_hip
+        if fc_weight.shape[0] > 1:      # wide head: the multi-step horizon
+            return branch_fuse_head_multi_hip(branch_feats, fc_weight, fc_bias)
         return branch_fuse_head_hip(branch_feats, fc_weight, fc_bias)
     return ref.branch_fuse_head(branch_feats, fc_weight, fc_bias)

@@ -11,6 +11,8 @@ Kernel coverage (all landed; SURVEY §2.4 op numbers in parentheses):
     (wgrad.hip). GRU rides the 4-slot packing documented on FusedLSTMFn.
   - SeqsumPermuteFn (K3), GateFn (K4), HeadFn (K7), FusedMSELossFn (K8);
     the K9 Adam kernel is driven by train/fused_adam.py.
+  - HeadMultiFn (K7 with 2..32 output columns: the multi-step horizon) and
+    MaskedLossFn (K8 over non-NaN targets: MSE / MAE / Huber).
 The reduction kernels (wgrad, head wgrad, the gate's reduces) finish their own
 outputs — the last workgroup to arrive rounds the fp32 sums to the parameter
 dtype and writes the gradients in their final shapes — so the backward
@@ -400,6 +402,21 @@ def branch_fuse_head_hip(branch_feats, fc_weight, fc_bias):
     return ref.branch_fuse_head(branch_feats, fc_weight, fc_bias)
 
 
+def branch_fuse_head_multi_hip(branch_feats, fc_weight, fc_bias):
+    """The wide head (multi-step horizon, O = P*C >= 2 output columns) on the
+    MFMA kernels. ops.branch_fuse_head routes here on fc_weight.shape[0] > 1;
+    branch_fuse_head_hip stays the one-column entry with its own contract."""
+    O, G = fc_weight.shape
+    if (2 <= O <= 32 and G <= 64 and G % 8 == 0 and len(branch_feats) <= 3
+            and branch_feats[0].dtype in (torch.bfloat16, torch.float16)):
+        return HeadMultiFn.apply(fc_weight, fc_bias, *branch_feats)
+    _fallback(
+        f"fused wide head with C_out={O}, G={G}, M={len(branch_feats)}, "
+        f"dtype={branch_feats[0].dtype} (served: 2<=C_out<=32, G<=64 with "
+        "G%8==0, M<=3, bf16/f16)")
+    return ref.branch_fuse_head(branch_feats, fc_weight, fc_bias)
+
+
 class SeqsumPermuteFn(torch.autograd.Function):
     """K3: x_seq = obs.sum(-1).permute(0,2,1) as one kernel (reference
     STMGCN.py:36,39); backward broadcasts over T,C."""
@@ -500,3 +517,59 @@ class FusedMSELossFn(torch.autograd.Function):
         (diff,) = ctx.saved_tensors
         dpred = C.mse_bwd(diff, gout.detach().reshape(1).float().contiguous())
         return dpred, None
+
+
+class HeadMultiFn(torch.autograd.Function):
+    """K7 wide: y (B, N, O) = (sum_m feats_m) @ W^T + b for 2 <= O <= 32
+    output columns (multi-step horizon: column o = p*C + c) on the MFMA
+    kernels; fsum is rounded once and saved, the one dfeat tensor is handed to
+    every branch and the wgrad kernel finishes dW / db itself, as in HeadFn."""
+
+    @staticmethod
+    def forward(ctx, fc_weight, fc_bias, *feats):
+        C = require_hip()
+        dt = feats[0].dtype
+        y, fsum = C.head_multi_fwd(list(feats), fc_weight.to(dt),
+                                   fc_bias.to(dt))
+        ctx.save_for_backward(fc_weight, fsum)
+        ctx.M = len(feats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        C = require_hip()
+        fc_weight, fsum = ctx.saved_tensors
+        dy = dy.contiguous()
+        dfeat = C.head_multi_bwd(dy, fc_weight.to(dy.dtype))
+        if fc_weight.dtype == dy.dtype:   # rounded by the kernel itself
+            dw, db = C.head_multi_wgrad_grads(dy, fsum)
+        else:
+            dwf, dbf = C.head_multi_wgrad(dy, fsum)
+            dw, db = dwf.to(fc_weight.dtype), dbf.to(fc_weight.dtype)
+        return (dw, db) + (dfeat,) * ctx.M
+
+
+MASKED_LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2}
+
+
+class MaskedLossFn(torch.autograd.Function):
+    """K8 masked: mean of l(pred - target) over the non-NaN targets, l = MSE /
+    MAE / Huber(delta = 1). The loss and 1 / max(count_valid, 1) stay on the
+    device (no host read, capturable); diff is saved with 0 at masked elements,
+    which is all the backward needs (l'(0) = 0 for every kind)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind):
+        C = require_hip()
+        res, diff = C.masked_loss_fwd(pred, target, kind)
+        ctx.save_for_backward(diff, res)
+        ctx.kind = kind
+        return res[0]
+
+    @staticmethod
+    def backward(ctx, gout):
+        C = require_hip()
+        diff, res = ctx.saved_tensors
+        dpred = C.masked_loss_bwd(
+            diff, res, gout.detach().reshape(1).float().contiguous(), ctx.kind)
+        return dpred, None, None

@@ -163,3 +163,31 @@ def branch_fuse_head(branch_feats: List[torch.Tensor], fc_weight: torch.Tensor,
     (reference STMGCN.py:116-118)."""
     fused = torch.stack(branch_feats, dim=-1).sum(dim=-1)   # (B, N, G)
     return F.linear(fused, fc_weight, fc_bias)              # (B, N, C)
+
+
+def masked_loss(pred: torch.Tensor, target: torch.Tensor,
+                kind: str = "mse") -> torch.Tensor:
+    """Loss over the valid targets only; a NaN target marks a missing reading.
+
+    valid = target == target; loss = sum_valid l(pred - target) /
+    max(count_valid, 1) with l = d^2 (mse), |d| (mae) or Huber with delta = 1
+    (huber, as SmoothL1Loss). The gradient is gout * l'(d) / max(count, 1) on
+    valid elements and exactly 0 elsewhere (the NaN never enters a product);
+    abs'(0) = 0. Every target masked: loss 0, zero gradient.
+    bf16 / f16 inputs form the sum in fp32 (an f16 sum of a few 10^4 terms
+    overflows) and return an fp32 scalar, as the fused kernel does."""
+    valid = target == target
+    d = torch.where(valid, pred - target, torch.zeros_like(pred))
+    if kind == "mse":
+        l = d * d
+    elif kind == "mae":
+        l = d.abs()
+    elif kind == "huber":
+        a = d.abs()
+        l = torch.where(a < 1, 0.5 * d * d, a - 0.5)
+    else:
+        raise ValueError(f"unknown masked loss kind {kind!r}")
+    if l.dtype in (torch.bfloat16, torch.float16):
+        l = l.float()
+    count = valid.sum().clamp(min=1).to(l.dtype)
+    return l.sum() / count

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .metrics import MSE, RMSE, MAE, MAPE, PCC
+from .metrics import MSE, RMSE, MAE, MAPE, PCC, masked_metrics
 
 
 class ModelTrainer:
@@ -271,8 +271,16 @@ class ModelTrainer:
                     preds.append(y_pred.float().cpu().numpy())
                 gt = data_class.minmax_denormalize(np.concatenate(truths, axis=0))
                 pr = data_class.minmax_denormalize(np.concatenate(preds, axis=0))
-                results[mode] = {"MSE": MSE(pr, gt), "RMSE": RMSE(pr, gt),
-                                 "MAE": MAE(pr, gt), "MAPE": MAPE(pr, gt)}
+                if gt.ndim == 4:
+                    # horizon P > 1, (S, N, P, C): one record per step ahead,
+                    # then the aggregate over all steps below
+                    for p in range(gt.shape[2]):
+                        m = masked_metrics(pr[:, :, p], gt[:, :, p])
+                        self._log(f"{mode} step {p + 1} true MSE: ", m["MSE"],
+                                  " RMSE: ", m["RMSE"], " MAE: ", m["MAE"],
+                                  " MAPE: ", m["MAPE"] * 100, "%")
+                        self._emit({"test_mode": mode, "step": p, **m})
+                results[mode] = masked_metrics(pr, gt)
                 self._log(f"{mode} true MSE: ", results[mode]["MSE"])
                 self._log(f"{mode} true RMSE: ", results[mode]["RMSE"])
                 self._log(f"{mode} true MAE: ", results[mode]["MAE"])
