@@ -488,14 +488,22 @@ extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
 // The kernel is latency-bound (two workgroups per CU, a serial dh chain), so
 // a (layer, t) stage is laid out around what each s_waitcnt has to retire;
 // vmcnt retires in issue order (profiles/lstm_bwd_stage_waits.md):
-//   layer prologue     the lane's 8 W_hh^T fragments -> its LDS slots
-//   pointwise phase    no vector-memory wait (all saves come from lane-private
-//                      LDS slots; the top layer's dout loads are the exception);
-//                      the scalar-input layer 0 reduces its dx partials (DPP)
+//   layer prologue     the lane's 8 W_hh^T fragments -> its LDS slots; a top
+//                      layer that returns only the last step takes dout as
+//                      its initial dh_rec here
+//   pointwise phase    one straight-line body per layer form (layer_body), no
+//                      branch and no vector-memory wait (all saves come from
+//                      lane-private LDS slots; a ret_seq top layer's dout
+//                      loads, waited for once, are the exception); the dA
+//                      tile goes to LDS as a [gate column][row] image, 8 x
+//                      ds_write_b64; the scalar-input layer 0 alone computes
+//                      and reduces its dx partials (DPP)
 //   issue              W_ih^T fragments (L2), THEN the next stage's saves
 //                      (gates, c, upstream dh: HBM), THEN the dA stores
 //   barrier            dA tile visible
-//   GEMM1 + GEMM2      W_hh^T from LDS (lgkmcnt only); counted waits on W_ih^T
+//   GEMM1 + GEMM2      A fragments by ds_read_b64_tr_b16 (EXEC is all ones:
+//                      every branch around a stage is workgroup-uniform);
+//                      W_hh^T from LDS (lgkmcnt only); counted waits on W_ih^T
 //                      that leave the saves and the stores in flight
 //   dx / dh_g stores
 //   stage-in           the one wait for the saves; the stores stay in flight
@@ -512,13 +520,42 @@ template <typename T> __device__ __forceinline__ unsigned long pack4_word(f32x4 
 }
 
 // v + (v of the lane that DPP control CTRL pairs this lane with, same row)
+// (every lane of the row is read and written — full row / bank masks and
+// controls that pair each lane with a lane of its row — so bound_ctrl changes
+// no value; it frees the move's `old` operand, and the move folds into the add)
 template <int CTRL> __device__ __forceinline__ float dpp_row_add(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(
-                 0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+                 0, __float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
-__device__ __forceinline__ int swzA(int s, int cbyte) {      // dA rows: 512 B
-  return s * 512 + (cbyte ^ ((s & 15) << 4));
+// The dA tile in LDS is a [gate column c = 0..255][tile row s = 0..31] image
+// with 64 B rows: the dgrad GEMMs sum over the gate column, which is the LANE
+// index of the pointwise layout, so the tile is written as it falls (a lane's
+// rows 4*lgrp + r of one (gate slot, m-tile) are 8 contiguous bytes: 8-byte
+// slot 4*m + lgrp of row c) and read back transposed by ds_read_b64_tr_b16.
+// The slot index is XORed with (c >> 1) & 7. Writes (32 banks, 16 consecutive
+// lanes = 16 consecutive c per access): c & 1 picks the 64 B half of the
+// 128 B bank row and (c >> 1) & 7 permutes the 8 slots of that half — 16
+// distinct 8 B bank pairs. Transposed reads (64 banks, 32 lanes per access =
+// image rows c0 .. c0+3 and c0+8 .. c0+11, four slots 4*m + p each): c & 3
+// picks the 64 B quarter of the 256 B bank row, and bit 3 of c flips bit 2 of
+// the slot, so the two row groups take the two halves of the quarter. Both
+// sides are conflict-free (profiles/lstm_bwd_pointwise.md).
+__device__ __forceinline__ int dA_img(int c, int slot) {
+  return c * 64 + ((slot ^ ((c >> 1) & 7)) << 3);
+}
+
+// a * b rounded to T, the last product of a dA value. bf16 rounds the fp32
+// product; f16 rounds the exact product once (v_fma_mixlo_f16), the form the
+// compiler picks for all but a few elements when the choice is left to it.
+template <typename T> __device__ __forceinline__ T stm_fmul_to(float a, float b) {
+  if constexpr (std::is_same<T, __half>::value) {
+    unsigned hw;
+    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hw) : "v"(a), "v"(b));
+    return __builtin_bit_cast(T, (unsigned short)hw);
+  } else {
+    return fromF<T>(stm_fmul(a, b));
+  }
 }
 
 // GRU backward (same packed-slot scheme as forward — see lstm_fwd_kernel):
@@ -556,7 +593,7 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   // the CIN1 dx reduction scratch, the lane-private parking of the saves and
   // the layer's W_hh^T. The cross-layer dh hand-off lives in GLOBAL scratch
   // dh_g.
-  char* dA_lds = lds;                         // [SEQ_TILE][512B] swizzled
+  char* dA_lds = lds;                         // [256 gate columns][64 B] (dA_img)
   float* red = (float*)(dA_lds + SEQ_TILE * 512);   // [4][SEQ_TILE] cross-wave scratch
   // lane-PRIVATE gates staging (each lane writes exactly the 2*MT fragments
   // it alone reads next stage -> no cross-wave visibility, no barrier, and
@@ -577,8 +614,33 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   char* wstage = cstage + 2 * 256 * (MT * 8);
   char* wmine = wstage + threadIdx.x * 16;
 
-  for (int layer = L - 1; layer >= 0; --layer) {
-    const bool l0cin1 = CIN1 && layer == 0;
+  // the lane's part of the dA image addresses: its two 8-byte write slots of
+  // row hch (the gate slot q adds q * 4096) and the four read pieces of a
+  // k-step (lane 4*qq + p of a 16-lane group names row qq, slot 4*m + p of
+  // the group's 4-row block; the k-step kk adds kk * 2048)
+  int dA_wr[MT], dA_rd[2][MT];
+  #pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    dA_wr[m] = dA_img(hch, 4 * m + lgrp);
+    #pragma unroll
+    for (int hf = 0; hf < 2; ++hf)
+      dA_rd[hf][m] = dA_img(8 * lgrp + 4 * hf + (l16 >> 2), 4 * m + (l16 & 3));
+  }
+
+  // One layer: a straight-line body per combination of the workgroup-uniform
+  // conditions SCALAR (the scalar-input layer 0 of a cin = 1 model: no input
+  // GEMM, its dx is the rank-1 term reduced in the pointwise phase) and where
+  // dh comes from besides the recurrent carry — DH_UP: the layer above
+  // (dh_g), DH_SEQ: dout at every stage (top layer, ret_seq), DH_LAST: dout
+  // at the last timestep only (top layer, the flagship), where dh_rec is
+  // still 0: it IS the initial dh_rec, loaded in the layer prologue, and the
+  // t loop holds no dout code. A stage then holds no code of another form and
+  // no per-element branch: the pointwise phase is bound by instruction issue
+  // (profiles/lstm_bwd_pointwise.md).
+  constexpr int DH_UP = 0, DH_SEQ = 1, DH_LAST = 2;
+  auto layer_body = [&](int layer, auto scalar_c, auto src_c) {
+    constexpr bool SCALAR = CIN1 && decltype(scalar_c)::value;
+    constexpr int SRC = decltype(src_c)::value;
     const T* WhhT = (const T*)w.w_hh[layer];  // (H, 4H)
     const T* WihT = (const T*)w.w_ih[layer];  // (Cin_l, 4H)
     float dh_rec[MT][4], dc[MT][4];
@@ -586,6 +648,44 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
     for (int m = 0; m < MT; ++m)
       #pragma unroll
       for (int r = 0; r < 4; ++r) { dh_rec[m][r] = 0.f; dc[m][r] = 0.f; }
+
+    // top layer: the lane's 8 dout values of one timestep, loaded back to back
+    // and waited for once. Tail rows load the tile's last valid row (always in
+    // bounds) and are masked by a select at their use, not by a branch around
+    // the load.
+    auto load_dout = [&](const T* dtile, int dstride, T (&dov)[MT][4]) {
+      const int last = S - 1 - s0;
+      #pragma unroll
+      for (int m = 0; m < MT; ++m)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * m + 4 * lgrp + r;
+          dov[m][r] = dtile[(row < last ? row : last) * dstride + hch];
+        }
+    };
+    // ... as fp32, all eight defined at one point: the empty asm is that one
+    // wait, and it keeps the compiler from sinking a load into a branch of its
+    // own around the element that uses it
+    auto dout_f32 = [&](const T (&dov)[MT][4], float (&dof)[MT][4]) {
+      #pragma unroll
+      for (int m = 0; m < MT; ++m)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) dof[m][r] = toF<T>(dov[m][r]);
+      static_assert(MT == 2, "eight operands");
+      asm volatile("" : "+v"(dof[0][0]), "+v"(dof[0][1]), "+v"(dof[0][2]), "+v"(dof[0][3]),
+                        "+v"(dof[1][0]), "+v"(dof[1][1]), "+v"(dof[1][2]), "+v"(dof[1][3]));
+    };
+    if constexpr (SRC == DH_LAST) {
+      T dov[MT][4];
+      float dof[MT][4];
+      load_dout(dout + (long)s0 * RNN_H, RNN_H, dov);
+      dout_f32(dov, dof);
+      #pragma unroll
+      for (int m = 0; m < MT; ++m)
+        #pragma unroll
+        for (int r = 0; r < 4; ++r)   // 0 + x: what the stage's dh_rec + dout gave
+          dh_rec[m][r] = (s0 + 16 * m + 4 * lgrp + r < S) ? stm_fadd(0.f, dof[m][r]) : 0.f;
+    }
 
     // ---- training-save prefetch pipeline: gates/cseq (and the upstream dh)
     // for step t are loaded during stage t+1 and parked in the lane's LDS
@@ -625,7 +725,7 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
     auto cmine = [&](int t) {
       return (ulong1*)(cstage + ((t & 1) * 256 + threadIdx.x) * (MT * 8));
     };
-    if (layer < L - 1) {
+    if constexpr (SRC == DH_UP) {
       #pragma unroll
       for (int m = 0; m < MT; ++m)
         dhmine[m] = *(const ulong1*)(dh_at(Tst - 1) + lane_frag(m) * 4);
@@ -647,7 +747,7 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
     }
     // scalar-input layer 0: this lane's four W_ih values, once per layer
     float wih0[4];
-    if (l0cin1) {
+    if constexpr (SCALAR) {
       #pragma unroll
       for (int q = 0; q < 4; ++q) wih0[q] = toF<T>(WihT[q * 64 + hch]);
     }
@@ -666,37 +766,35 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       // 4*m + r (common.h) -> one 16 B piece per gate slot
       alignas(16) T pk[4][MT * 4];
 
-      // top layer: the lane's 8 dout values, loaded back to back and waited
-      // for once. Tail rows load the tile's last valid row (always in bounds)
-      // and are masked by a select below, not by a branch around the load.
-      const bool top_dout = layer == L - 1 && (ret_seq || t == Tst - 1);
-      T dov[MT][4];
-      if (top_dout) {
-        // workgroup-uniform tile base + small per-lane offsets
-        const int dstride = ret_seq ? Tst * RNN_H : RNN_H;
-        const T* dtile = dout + (long)s0 * dstride + (ret_seq ? t * RNN_H : 0);
-        const int last = S - 1 - s0;
-        // (the empty asm keeps the 8 offsets from being carried in registers
-        // through the whole kernel for a load that most stages do not issue)
-        int row0 = 4 * lgrp;
-        asm volatile("" : "+v"(row0));
-        #pragma unroll
-        for (int m = 0; m < MT; ++m)
-          #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = 16 * m + row0 + r;
-            dov[m][r] = dtile[(row < last ? row : last) * dstride + hch];
-          }
+      // the stage's dout (the one vector-memory wait of a pointwise phase)
+      float dof[MT][4];
+      if constexpr (SRC == DH_SEQ) {
+        T dov[MT][4];
+        load_dout(dout + ((long)s0 * Tst + t) * RNN_H, Tst * RNN_H, dov);
+        dout_f32(dov, dof);
       }
 
+      // Every rounding below is pinned (stm_fmul / stm_fadd / fmaf /
+      // stm_fmul_to), one form per cell type: the form most elements had when
+      // the arithmetic was left to the compiler's FMA contraction. That fused
+      // only the LSTM's dc + (dh o)(1 - tc^2) and the scalar-input term's
+      // chain; 1 - v^2 is a rounded square taken from 1, every other product
+      // is rounded on its own (the few elements that deviated are listed in
+      // profiles/lstm_bwd_pointwise.md).
       #pragma unroll
       for (int m = 0; m < MT; ++m) {
         frag gf0 = *(const frag*)&gmine[m * 32 + 0];                 // i|f
         frag gf1 = *(const frag*)&gmine[m * 32 + 16];                // g|o
         const ulong1 cc_t = cmine(t)[m];
-        const ulong1 cc_p = (!GRU && t > 0) ? cmine(t - 1)[m] : ulong1{0};
+        // (read unconditionally, then selected: at t == 0 the other parity
+        // slot holds the dead c_1, and c_{-1} = 0)
+        ulong1 cc_p = ulong1{0};
+        if constexpr (!GRU) {
+          cc_p = cmine(t - 1)[m];
+          cc_p = t > 0 ? cc_p : ulong1{0};
+        }
         ulong1 dhup = ulong1{0};
-        if (layer < L - 1) dhup = dhmine[m];
+        if constexpr (SRC == DH_UP) dhup = dhmine[m];
         f32x4 ct, cpv;
         #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -707,49 +805,55 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
         for (int r = 0; r < 4; ++r) {
           const int row = 16 * m + 4 * lgrp + r;
           float dh = dh_rec[m][r];
-          if (layer < L - 1) {
-            dh += elemF(((const elem*)&dhup)[r]);
-          } else if (top_dout) {
-            dh = (s0 + row < S) ? dh + toF<T>(dov[m][r]) : dh;
+          if constexpr (SRC == DH_UP) {
+            dh = stm_fadd(dh, elemF(((const elem*)&dhup)[r]));
+          } else if constexpr (SRC == DH_SEQ) {
+            dh = (s0 + row < S) ? stm_fadd(dh, dof[m][r]) : dh;
           }
-          float dAi, dAf, dAg, dAo;
-          if (GRU) {
+          // the dA values as (a, b) of their last product a * b: rounded to T
+          // for the tile and the stream, in fp32 for the scalar-input term
+          float fa[4], fb[4];
+          if constexpr (GRU) {
             // gf0 = [r, z], gf1 = [n, Bn]; ct = h_{t-1} (fwd csave)
             const float r_ = elemF(gf0[r]);
             const float z_ = elemF(gf0[4 + r]);
             const float n_ = elemF(gf1[r]);
             const float Bn = elemF(gf1[4 + r]);
             const float hprev = ct[r];
-            dh += dc[m][r];                       // direct dh_t * z carry
-            const float dz_pre = dh * (hprev - n_) * z_ * (1.f - z_);
-            const float dn_pre = dh * (1.f - z_) * (1.f - n_ * n_);
-            const float dBn = dn_pre * r_;
-            const float dr_pre = dn_pre * Bn * r_ * (1.f - r_);
-            dc[m][r] = dh * z_;
-            dAi = dr_pre; dAf = dz_pre; dAg = dn_pre; dAo = dBn;
+            dh = stm_fadd(dh, dc[m][r]);          // direct dh_t * z carry
+            const float dnp = stm_fmul(dh, 1.f - z_);
+            const float dnq = 1.f - stm_fmul(n_, n_);
+            const float dn_pre = stm_fmul(dnp, dnq);
+            fa[0] = stm_fmul(stm_fmul(dn_pre, Bn), r_); fb[0] = 1.f - r_;     // dr_pre
+            fa[1] = stm_fmul(stm_fmul(dh, hprev - n_), z_); fb[1] = 1.f - z_; // dz_pre
+            fa[2] = dnp; fb[2] = dnq;                                         // dn_pre
+            fa[3] = dn_pre; fb[3] = r_;                                       // dBn
+            dc[m][r] = stm_fmul(dh, z_);
           } else {
             const float i_ = elemF(gf0[r]);
             const float f_ = elemF(gf0[4 + r]);
             const float g_ = elemF(gf1[r]);
             const float o_ = elemF(gf1[4 + r]);
             const float tc = stm_tanh(ct[r]);
-            float dcv = dc[m][r] + dh * o_ * (1.f - tc * tc);
-            dAo = dh * tc * o_ * (1.f - o_);
-            dAi = dcv * g_ * i_ * (1.f - i_);
-            dAf = dcv * cpv[r] * f_ * (1.f - f_);
-            dAg = dcv * i_ * (1.f - g_ * g_);
-            dc[m][r] = dcv * f_;
+            const float dcv = fmaf(stm_fmul(dh, o_), 1.f - stm_fmul(tc, tc), dc[m][r]);
+            fa[0] = stm_fmul(stm_fmul(dcv, g_), i_); fb[0] = 1.f - i_;        // dAi
+            fa[1] = stm_fmul(stm_fmul(dcv, cpv[r]), f_); fb[1] = 1.f - f_;    // dAf
+            fa[2] = stm_fmul(dcv, i_); fb[2] = 1.f - stm_fmul(g_, g_);        // dAg
+            fa[3] = stm_fmul(stm_fmul(dh, tc), o_); fb[3] = 1.f - o_;         // dAo
+            dc[m][r] = stm_fmul(dcv, f_);
           }
-          pk[0][4 * m + r] = fromF<T>(dAi);
-          pk[1][4 * m + r] = fromF<T>(dAf);
-          pk[2][4 * m + r] = fromF<T>(dAg);
-          pk[3][4 * m + r] = fromF<T>(dAo);
           #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *(T*)&dA_lds[swzA(row, (q * 64 + hch) * 2)] = pk[q][4 * m + r];
-          if (l0cin1)
-            dxpart[m][r] = dAi * wih0[0] + dAf * wih0[1] + dAg * wih0[2] + dAo * wih0[3];
+          for (int q = 0; q < 4; ++q) pk[q][4 * m + r] = stm_fmul_to<T>(fa[q], fb[q]);
+          if constexpr (SCALAR)   // dx partial: one fma chain, W_ih[q] the lane's four
+            dxpart[m][r] = fmaf(stm_fmul(fa[3], fb[3]), wih0[3],
+                           fmaf(stm_fmul(fa[2], fb[2]), wih0[2],
+                           fmaf(stm_fmul(fa[0], fb[0]), wih0[0],
+                                stm_fmul(stm_fmul(fa[1], fb[1]), wih0[1]))));
         }
+        // the m-tile's part of the dA image: one 8-byte word per gate slot
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *(unsigned long*)&dA_lds[q * 4096 + dA_wr[m]] = *(const unsigned long*)&pk[q][4 * m];
       }
       // ---- dA stream for the wgrad kernel, tile order (common.h): the lane's
       // 4 x 16 B pieces; a wave's store per gate slot covers 1 KiB contiguous.
@@ -758,7 +862,7 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       // stored after the GEMMs. A store issued here would be drained by GEMM1's
       // first weight-fragment wait (vmcnt retires in order) on the serial
       // dh_prev path: ~1% slower, profiles/r03_da_stream_layout.md.
-      if (l0cin1) {
+      if constexpr (SCALAR) {
         // CIN1 l0: dx[s,t] = sum_g dA[s,g] W_ih[g,0], reduced here so that
         // the dA barrier below also publishes the per-wave sums. The 16 lanes of an l16
         // group are one DPP row: quad_perm pairs lanes xor 1 and xor 2, then
@@ -780,19 +884,22 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
         #pragma unroll
         for (int m = 0; m < MT; ++m)
           #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float v = dpp_row_add<0x140>(dxpart[m][r]);
-            if (l16 == 0) red[wv * SEQ_TILE + 16 * m + 4 * lgrp + r] = v;
-          }
+          for (int r = 0; r < 4; ++r) dxpart[m][r] = dpp_row_add<0x140>(dxpart[m][r]);
+        if (l16 == 0) {   // one predicated region: the row's 4 sums per m-tile, 16 B
+          #pragma unroll
+          for (int m = 0; m < MT; ++m)
+            *(f32x4*)&red[wv * SEQ_TILE + 16 * m + 4 * lgrp] =
+                f32x4{dxpart[m][0], dxpart[m][1], dxpart[m][2], dxpart[m][3]};
+        }
       }
       T* out_dA = dA_g + stm_da_tile_off(base * S_pad + s0);
       #pragma unroll
       for (int q = 0; q < 4; ++q) *(frag*)&gmine[q * 16] = *(const frag*)pk[q];
-      // ---- the rest of the stage, one straight-line body per combination of
-      // the workgroup-uniform conditions (REC: t > 0, a recurrent GEMM and a
-      // next stage exist; INP: the layer has an input GEMM, all but the
-      // scalar-input layer 0; UP: a layer above hands dh down), so that every
-      // wait in it is counted against loads that are certainly in flight.
+      // ---- the rest of the stage, one straight-line body per value of REC
+      // (t > 0: a recurrent GEMM and a next stage exist) inside the layer's
+      // form (INP: the layer has an input GEMM, all but the scalar-input
+      // layer 0; UP: a layer above hands dh down), so that every wait in it is
+      // counted against loads that are certainly in flight.
       //
       // dgrad GEMMs: dh_prev = dA @ W_hh (GEMM1) and dx = dA @ W_ih (GEMM2)
       // from ONE K loop. Both read the same 16 A fragments of the dA tile, so
@@ -808,10 +915,10 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
       // untouched at the end of the stage, the one place that waits for them;
       // the dA stores are issued right behind them, the dx / dh_g stores after
       // the GEMMs, and neither is waited for.
-      auto stage_rest = [&](auto rec_c, auto inp_c, auto up_c) {
+      auto stage_rest = [&](auto rec_c) {
         constexpr bool REC = decltype(rec_c)::value;
-        constexpr bool INP = decltype(inp_c)::value;
-        constexpr bool UP = decltype(up_c)::value;
+        constexpr bool INP = !SCALAR;
+        constexpr bool UP = SRC == DH_UP;
         // row hch of W_ih^T, as a 32-bit byte offset from the uniform pointer
         const unsigned wlane = (hch * (4 * RNN_H) + lgrp * 8) * sizeof(T);
         frag b2[2][4];
@@ -834,8 +941,18 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
               #pragma unroll
               for (int j = 0; j < 2; ++j)
                 #pragma unroll
-                for (int m = 0; m < MT; ++m)
-                  a[j][m] = *(const frag*)&dA_lds[swzA(16 * m + l16, ((4 * h + jb + j) * 32 + lgrp * 8) * 2)];
+                for (int m = 0; m < MT; ++m) {
+                  // A[16m + l16][32 kk + 8 lgrp + 0..7]: two transposed reads
+                  // of 4 gate columns each, the k order of a row-major fragment
+                  typedef short short4v __attribute__((ext_vector_type(4)));
+                  typedef short short8v __attribute__((ext_vector_type(8)));
+                  typedef __attribute__((address_space(3))) short4v* lds_s4;
+                  const char* p = dA_lds + (4 * h + jb + j) * 2048;
+                  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(p + dA_rd[0][m]));
+                  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(p + dA_rd[1][m]));
+                  a[j][m] = __builtin_bit_cast(
+                      frag, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+                }
               #pragma unroll
               for (int j = 0; j < 2; ++j)
                 #pragma unroll
@@ -949,23 +1066,29 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
           __syncthreads();   // the next pointwise phase overwrites dA / red
         }
       };
-      auto stage_rest_for = [&](auto rec_c) {
-        rnn_uniform_bool(!l0cin1, [&](auto inp_c) {
-          rnn_uniform_bool(layer < L - 1, [&](auto up_c) {
-            stage_rest(rec_c, inp_c, up_c);
-          });
-        });
-      };
       // The last stage leaves the loop on its own edge: its dA stores are
       // still in flight, and if that state reached the loop header every
       // stage would drain its stores at the top.
       if (t == 0) {
-        stage_rest_for(std::false_type{});
+        stage_rest(std::false_type{});
         break;
       }
-      stage_rest_for(std::true_type{});
+      stage_rest(std::true_type{});
     }  // t loop
-  }  // layer loop
+  };  // layer_body
+
+  for (int layer = L - 1; layer >= 0; --layer) {
+    rnn_uniform_bool(CIN1 && layer == 0, [&](auto scalar_c) {
+      if (layer < L - 1) {
+        layer_body(layer, scalar_c, std::integral_constant<int, DH_UP>{});
+      } else {
+        rnn_uniform_bool(ret_seq != 0, [&](auto seq_c) {
+          layer_body(layer, scalar_c,
+                     std::integral_constant<int, decltype(seq_c)::value ? DH_SEQ : DH_LAST>{});
+        });
+      }
+    });
+  }
 }
 
 extern "C" void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout,
