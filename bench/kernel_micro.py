@@ -1,7 +1,7 @@
 """Standalone kernel microbenchmarks (GPU) — per-kernel wall time via HIP
 events, for tuning without running the whole model.
 
-Usage: python bench/kernel_micro.py [--kernel lstm_wgrad|atb_wgrad|lstm|dual_gconv|all]
+Usage: python bench/kernel_micro.py [--kernel lstm_wgrad|atb_wgrad|lstm|dual_gconv|cheb|all]
 Prints one JSON line per measurement.
 """
 from __future__ import annotations
@@ -121,6 +121,46 @@ def bench_dual_gconv(C):
                       "ratio": round(res["dual_gconv"] / res["cheb_gconv_k2"], 3)}))
 
 
+def bench_cheb(C):
+    """Fused ChebConv at the bench-1024 gconv shape (B = 32, N = 1024,
+    C = Cout = 64, bf16, K_s = 3, training) on the preset's three graphs:
+    forward, then dX + the finishing wgrad, as the train step runs them.
+    This is the case the SQ wait counters of cheb_fused_fwd / cheb_fused_bwd /
+    atb_wgrad are collected on."""
+    from stmgcn_amd import PRESETS
+    from stmgcn_amd.data.synthetic import make_synthetic_dataset
+    from stmgcn_amd.graph import SupportGenerator
+    from stmgcn_amd.ops.hip_ops import ChebGconvFn
+    cfg = PRESETS["bench-1024"]
+    B, N, Cin, Cout = cfg.batch_size, cfg.n_nodes, 64, 64
+    raw = make_synthetic_dataset(n_nodes=N, n_steps=64, m_graphs=cfg.m_graphs,
+                                 seed=7, day_timesteps=1)
+    gen = SupportGenerator(cfg.kernel_type, cfg.cheby_K, cfg.lambda_max_mode)
+    for key in [k for k in raw if k.endswith("_adj")]:
+        csr = gen.process_csr(torch.from_numpy(raw[key]).float()).to("cuda")
+        x = torch.randn(B, N, Cin, device="cuda", dtype=torch.bfloat16,
+                        requires_grad=True)
+        W = (torch.randn(csr.K_supports * Cin, Cout, device="cuda",
+                         dtype=torch.bfloat16) * 0.1).requires_grad_(True)
+        b = torch.zeros(Cout, device="cuda", dtype=torch.bfloat16,
+                        requires_grad=True)
+        dy = torch.randn(B, N, Cout, device="cuda", dtype=torch.bfloat16)
+
+        def fwd():
+            with torch.no_grad():
+                ChebGconvFn.apply(x, W, b, csr, "relu", True)
+
+        def step():
+            y = ChebGconvFn.apply(x, W, b, csr, "relu", True)
+            torch.autograd.grad(y, (x, W, b), dy)
+        us_f = timeit(fwd, iters=200, warmup=20)
+        us_s = timeit(step, iters=200, warmup=20)
+        print(json.dumps({"kernel": "cheb_gconv_" + key, "fwd_us": round(us_f, 1),
+                          "fwd_bwd_us": round(us_s, 1),
+                          "supports": csr.K_supports,
+                          "nnz_per_row": round(csr.nnz / N, 2)}))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--kernel", default="all")
@@ -135,6 +175,8 @@ def main():
         bench_lstm(C)
     if args.kernel in ("dual_gconv", "all"):
         bench_dual_gconv(C)
+    if args.kernel in ("cheb", "all"):
+        bench_cheb(C)
 
 
 if __name__ == "__main__":

@@ -12,10 +12,14 @@
 // spmm_step computes one recurrence step as a fused SpMM + axpby:
 //     out = alpha * (G @ xin) + beta * p1 + gamma * p2
 // over (B, N, C) slices embedded in a (B, N, K, C) stack (per-tensor row
-// strides). Thread mapping: 256-thread blocks; each thread owns one (row,
-// channel) pair, so a row's C channels sit in consecutive lanes and every
-// gather xin[col, c] is a coalesced C-wide segment. Host-side sequencing of
-// the K steps lives in bindings.cpp (cheb_apply / cheb_combine via Clenshaw).
+// strides). Thread mapping of spmm_step: 256-thread blocks; each thread owns
+// one (row, channel) pair, so a row's C channels sit in consecutive lanes and
+// every gather xin[col, c] is a coalesced C-wide segment. Host-side sequencing
+// of the K steps lives in bindings.cpp (cheb_apply / cheb_combine via
+// Clenshaw). The fused kernels below map a thread to one (row, 8-channel
+// group) unit when the channel count allows (gconv_tile.h, gc_vec8): one pass
+// per 32-row tile, 16-byte accesses, the gather's loads in flight together,
+// and in the backward the gather issued before the dz staging and the U GEMM.
 
 #include "gconv_tile.h"
 
@@ -77,7 +81,7 @@ __global__ void spmm_step_kernel(
 // p1 is read only at the thread's own (row, c) element, so p1 == pout
 // aliasing is safe (the gather operand xin must be a distinct buffer).
 template <typename T, bool MF>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 4)
 cheb_fused_fwd_kernel(const int* __restrict__ rowptr,
                       const int* __restrict__ colidx,
                       const float* __restrict__ vals,
@@ -86,7 +90,7 @@ cheb_fused_fwd_kernel(const int* __restrict__ rowptr,
                       const T* __restrict__ W, const T* __restrict__ bias,
                       T* __restrict__ pout, float* __restrict__ yacc,
                       T* __restrict__ yout, int N, int C, int Cout, int kofs,
-                      float alpha, float beta, int first, int act) {
+                      float alpha, float beta, int first, int act, int vec) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * GC_ST;
   extern __shared__ char lds[];
@@ -96,36 +100,82 @@ cheb_fused_fwd_kernel(const int* __restrict__ rowptr,
   const T* pb = p1 ? p1 + (long)b * N * C : nullptr;
   const T* x0b = x0 ? x0 + (long)b * N * C : nullptr;
 
-  // ---- phase 1: recurrence (SpMM + axpby), tile staged in LDS ----
-  for (int i = threadIdx.x; i < GC_ST * C; i += 256) {
-    const int c = i % C, rl = i / C;
-    const int row = n0 + rl;
-    float acc = 0.f;
-    if (x0b != nullptr)
-      gc_tile_store<T, MF>(l0, rl, c, (row < N) ? toF<T>(x0b[(long)row * C + c]) : 0.f);
-    if (row < N) {
-      if (xb != nullptr && alpha != 0.f) {
-        acc = gc_gather<T>(g, xb, row, C, c);
-        acc *= alpha;
-      }
-      if (pb != nullptr) acc = fmaf(beta, toF<T>(pb[(long)row * C + c]), acc);
-      if (pout != nullptr) pout[((long)b * N + row) * C + c] = fromF<T>(acc);
+  // ---- phase 0 (MFMA mix): what phase 2 reads from global memory, requested
+  // now so that it arrives under the gather ----
+  const GcLane l;
+  GcMixB<T> wk = {}, w0 = {};
+  GcYPrev yp = {};
+  if constexpr (MF) {
+    if (l.wv < (Cout >> 4)) {
+      wk = gc_mix_load<T>(W, kofs, C, Cout, l);
+      if (x0 != nullptr) w0 = gc_mix_load<T>(W, 0, C, Cout, l);
+      yp = gc_y_prefetch<T>(b, n0, N, Cout, l, bias, yacc, yout, first);
     }
-    if (W != nullptr) gc_tile_store<T, MF>(lds, rl, c, acc);
+  }
+
+  // ---- phase 1: recurrence (SpMM + axpby), tile staged in LDS ----
+  if (vec) {
+    // one (row, 8-channel group) unit per thread; at C = 64 a single pass
+    const int G = C >> 3;
+    for (int u = threadIdx.x; u < GC_ST * G; u += 256) {
+      const int rl = u / G, c = (u % G) * 8;
+      const int row = n0 + rl;
+      const bool live = row < N;
+      float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      GcRaw8<T> r0 = {}, rp = {};
+      if (live && x0b != nullptr) r0 = gc_load8<T>(&x0b[(long)row * C + c]);
+      if (live && pb != nullptr) rp = gc_load8<T>(&pb[(long)row * C + c]);
+      if (live) {
+        if (xb != nullptr && alpha != 0.f) {
+          gc_gather8<T>(g, xb, row, C, c, acc);
+          #pragma unroll
+          for (int q = 0; q < 8; ++q) acc[q] = stm_fmul(acc[q], alpha);
+        }
+        if (pb != nullptr) {
+          float pv[8];
+          gc_unpack8<T>(rp, pv);
+          #pragma unroll
+          for (int q = 0; q < 8; ++q) acc[q] = fmaf(beta, pv[q], acc[q]);
+        }
+        if (pout != nullptr) gc_store8<T>(&pout[((long)b * N + row) * C + c], acc);
+      }
+      if (x0b != nullptr) {
+        float v0[8];
+        gc_unpack8<T>(r0, v0);
+        gc_tile_store8<T, MF>(l0, rl, c, v0);
+      }
+      if (W != nullptr) gc_tile_store8<T, MF>(lds, rl, c, acc);
+    }
+  } else {
+    for (int i = threadIdx.x; i < GC_ST * C; i += 256) {
+      const int c = i % C, rl = i / C;
+      const int row = n0 + rl;
+      float acc = 0.f;
+      if (x0b != nullptr)
+        gc_tile_store<T, MF>(l0, rl, c, (row < N) ? toF<T>(x0b[(long)row * C + c]) : 0.f);
+      if (row < N) {
+        if (xb != nullptr && alpha != 0.f) {
+          acc = gc_gather<T>(g, xb, row, C, c);
+          acc *= alpha;
+        }
+        if (pb != nullptr) acc = fmaf(beta, toF<T>(pb[(long)row * C + c]), acc);
+        if (pout != nullptr) pout[((long)b * N + row) * C + c] = fromF<T>(acc);
+      }
+      if (W != nullptr) gc_tile_store<T, MF>(lds, rl, c, acc);
+    }
   }
   if (W == nullptr) return;
   __syncthreads();
 
   // ---- phase 2: mix epilogue y += tile @ W_k (+ x0 @ W_0) ----
   if constexpr (MF) {
-    const GcLane l;
     if (l.wv < (Cout >> 4)) {          // wave wv owns output cols [16wv,16wv+16)
       f32x4 acc[2];
       acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
       acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      gc_mix_mfma<T>(lds, W, kofs, C, Cout, l, acc);
-      if (x0 != nullptr) gc_mix_mfma<T>(l0, W, 0, C, Cout, l, acc);
-      gc_y_store_frag<T>(acc, b, n0, N, Cout, l, bias, yacc, yout, first, act);
+      gc_mix_mfma<T>(lds, wk, C, l, acc);
+      if (x0 != nullptr) gc_mix_mfma<T>(l0, w0, C, l, acc);
+      gc_y_store_frag<T>(acc, yp, b, n0, N, Cout, l, bias, yacc, yout, first, act);
     }
   } else {
     for (int i = threadIdx.x; i < GC_ST * Cout; i += 256) {
@@ -144,29 +194,61 @@ cheb_fused_fwd_kernel(const int* __restrict__ rowptr,
 // The U_j = dz W_j^T term is computed in-kernel from an LDS-staged dz tile —
 // the dgrad U stack (B,N,K_s,C) of the unfused design never exists.
 template <typename T, bool MF>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 4)
 cheb_fused_bwd_kernel(const int* __restrict__ rowptr,
                       const int* __restrict__ colidx,
                       const float* __restrict__ vals,
                       const T* __restrict__ xin, const T* __restrict__ p1,
                       const T* __restrict__ dz, const T* __restrict__ W,
                       T* __restrict__ out, int N, int C, int Cout, int kofs,
-                      float alpha, float beta) {
+                      float alpha, float beta, int vec, int vec_dz) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * GC_ST;
   extern __shared__ char lds[];
   float* ut = (float*)(lds + gc_slot_bytes(MF));
   const StmCsr g{rowptr, colidx, vals};
+  const T* xb = xin ? xin + (long)b * N * C : nullptr;
+  const T* pb = p1 ? p1 + (long)b * N * C : nullptr;
+
+  // ---- phase C's loads, first: the gather depends on neither dz, W nor U, so
+  // its round trips run under phases A and B. One (row, 8-channel group) unit
+  // per thread (C <= 64: the U tile's row stride), held in registers. ----
+  const int G = C >> 3;
+  const int rl = threadIdx.x / (G > 0 ? G : 1), c = (threadIdx.x % (G > 0 ? G : 1)) * 8;
+  const int row = n0 + rl;
+  const bool live = vec && rl < GC_ST && row < N;
+  float gth[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  GcRaw8<T> rp = {};
+  if (live) {
+    if (pb != nullptr) rp = gc_load8<T>(&pb[(long)row * C + c]);
+    if (xb != nullptr && alpha != 0.f) gc_gather8<T>(g, xb, row, C, c, gth);
+  }
 
   // ---- phase A: stage the dz tile;  phase B: U = dz @ W_j^T ----
-  gc_stage_dz<T, MF>(lds, dz + (long)b * N * Cout, n0, N, Cout);
+  gc_stage_dz<T, MF>(lds, dz + (long)b * N * Cout, n0, N, Cout, vec_dz);
   __syncthreads();
   gc_u_pass<T, MF>(lds, W, kofs, C, Cout, ut);
   __syncthreads();
 
   // ---- phase C: out = alpha*(G^T @ xin) + beta*p1 + U ----
-  const T* xb = xin ? xin + (long)b * N * C : nullptr;
-  const T* pb = p1 ? p1 + (long)b * N * C : nullptr;
+  if (vec) {
+    if (!live) return;
+    const float4* up = (const float4*)&ut[rl * 64 + c];
+    const float4 u0 = up[0], u1 = up[1];
+    float acc[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};
+    if (xb != nullptr && alpha != 0.f) {
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) acc[q] = fmaf(alpha, gth[q], acc[q]);
+    }
+    if (pb != nullptr) {
+      float pv[8];
+      gc_unpack8<T>(rp, pv);
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) acc[q] = fmaf(beta, pv[q], acc[q]);
+    }
+    gc_store8<T>(&out[((long)b * N + row) * C + c], acc);
+    return;
+  }
   for (int i = threadIdx.x; i < GC_ST * C; i += 256) {
     const int c = i % C, rl = i / C;
     const int row = n0 + rl;
@@ -190,7 +272,7 @@ void launch_fused_fwd(hipStream_t st, const ChebFwdArgs& a) {
                        a.g.colidx, a.g.vals, (const T*)a.xin, (const T*)a.p1,
                        (const T*)a.x0, (const T*)a.W, (const T*)a.bias, (T*)a.pout,
                        a.yacc, (T*)a.yout, a.N, a.C, a.Cout, a.kofs, a.alpha, a.beta,
-                       a.first, a.act);
+                       a.first, a.act, (int)gc_vec8(a.N, a.C, {a.xin, a.p1, a.x0, a.pout}));
   });
 }
 
@@ -203,7 +285,9 @@ void launch_fused_bwd(hipStream_t st, const ChebBwdArgs& a) {
                        gc_slot_bytes(MF) + GC_F32_TILE_BYTES, st, a.g.rowptr,
                        a.g.colidx, a.g.vals, (const T*)a.xin, (const T*)a.p1,
                        (const T*)a.dz, (const T*)a.W, (T*)a.out, a.N, a.C, a.Cout,
-                       a.kofs, a.alpha, a.beta);
+                       a.kofs, a.alpha, a.beta,
+                       (int)gc_vec8(a.N, a.C, {a.xin, a.p1, a.out}),
+                       (int)gc_vec8(a.N, a.Cout, {a.dz}));
   });
 }
 

@@ -29,7 +29,7 @@ namespace {
 // pbout) aliasing is safe per direction; the gather operands must be distinct
 // buffers.
 template <typename T, bool MF>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 4)
 dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
                       const T* __restrict__ xf, const T* pf1,
                       const T* __restrict__ xb, const T* pb1,
@@ -38,7 +38,7 @@ dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
                       T* pfout, T* pbout, float* __restrict__ yacc,
                       T* __restrict__ yout, int N, int C, int Cout,
                       int kofs_f, int kofs_b, float alpha, float beta,
-                      int first, int act) {
+                      int first, int act, int vec) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * GC_ST;
   extern __shared__ char lds[];
@@ -50,8 +50,57 @@ dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
   const T* xfb = xf + boff;
   const T* xbb = xb + boff;
 
+  // ---- phase 0 (MFMA mix): the yacc / bias reads of phase 2, requested
+  // ahead. The W fragments (three passes: 24 VGPRs) are fetched after the
+  // barrier here: held across two gathers they spill. ----
+  const GcLane l;
+  GcYPrev yp = {};
+  if constexpr (MF) {
+    if (l.wv < (Cout >> 4))
+      yp = gc_y_prefetch<T>(b, n0, N, Cout, l, bias, yacc, yout, first);
+  }
+
   // ---- phase 1: both recurrences (SpMM + axpby), tiles staged in LDS ----
-  for (int i = threadIdx.x; i < GC_ST * C; i += 256) {
+  const int G = C >> 3;
+  for (int u = threadIdx.x; vec && u < GC_ST * G; u += 256) {
+    // one (row, 8-channel group) unit per thread, both directions
+    const int rl = u / G, c = (u % G) * 8;
+    const int row = n0 + rl;
+    float af[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float ab[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float v0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (row < N) {
+      const long e = boff + (long)row * C + c;
+      GcRaw8<T> r0 = {}, rf = {}, rb = {};
+      if (x0 != nullptr) r0 = gc_load8<T>(&x0[e]);
+      if (pf1 != nullptr) rf = gc_load8<T>(&pf1[e]);
+      if (pb1 != nullptr) rb = gc_load8<T>(&pb1[e]);
+      gc_gather8<T>(gf, xfb, row, C, c, af);
+      gc_gather8<T>(gb, xbb, row, C, c, ab);
+      float pv[8];
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) af[q] = stm_fmul(alpha, af[q]);
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) ab[q] = stm_fmul(alpha, ab[q]);
+      if (pf1 != nullptr) {
+        gc_unpack8<T>(rf, pv);
+        #pragma unroll
+        for (int q = 0; q < 8; ++q) af[q] = fmaf(beta, pv[q], af[q]);
+      }
+      if (pb1 != nullptr) {
+        gc_unpack8<T>(rb, pv);
+        #pragma unroll
+        for (int q = 0; q < 8; ++q) ab[q] = fmaf(beta, pv[q], ab[q]);
+      }
+      gc_store8<T>(&pfout[e], af);
+      gc_store8<T>(&pbout[e], ab);
+      if (x0 != nullptr) gc_unpack8<T>(r0, v0);
+    }
+    gc_tile_store8<T, MF>(lf, rl, c, af);
+    gc_tile_store8<T, MF>(lb, rl, c, ab);
+    if (x0 != nullptr) gc_tile_store8<T, MF>(l0, rl, c, v0);
+  }
+  for (int i = threadIdx.x; !vec && i < GC_ST * C; i += 256) {
     const int c = i % C, rl = i / C;
     const int row = n0 + rl;
     float af = 0.f, ab = 0.f, v0 = 0.f;
@@ -73,15 +122,18 @@ dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
 
   // ---- phase 2: mix epilogue, one accumulator for all passes ----
   if constexpr (MF) {
-    const GcLane l;
     if (l.wv < (Cout >> 4)) {          // wave wv owns output cols [16wv,16wv+16)
       f32x4 acc[2];
       acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
       acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      gc_mix_mfma<T>(lf, W, kofs_f, C, Cout, l, acc);
-      gc_mix_mfma<T>(lb, W, kofs_b, C, Cout, l, acc);
-      if (x0 != nullptr) gc_mix_mfma<T>(l0, W, 0, C, Cout, l, acc);
-      gc_y_store_frag<T>(acc, b, n0, N, Cout, l, bias, yacc, yout, first, act);
+      const GcMixB<T> wf = gc_mix_load<T>(W, kofs_f, C, Cout, l);
+      const GcMixB<T> wb = gc_mix_load<T>(W, kofs_b, C, Cout, l);
+      GcMixB<T> w0 = {};
+      if (x0 != nullptr) w0 = gc_mix_load<T>(W, 0, C, Cout, l);
+      gc_mix_mfma<T>(lf, wf, C, l, acc);
+      gc_mix_mfma<T>(lb, wb, C, l, acc);
+      if (x0 != nullptr) gc_mix_mfma<T>(l0, w0, C, l, acc);
+      gc_y_store_frag<T>(acc, yp, b, n0, N, Cout, l, bias, yacc, yout, first, act);
     }
   } else {
     for (int i = threadIdx.x; i < GC_ST * Cout; i += 256) {
@@ -107,21 +159,40 @@ dual_fused_fwd_kernel(const StmCsr gf, const StmCsr gb,
 // The dz tile is staged once for both U GEMMs. pf1 == outf / pb1 == outb
 // aliasing is element-safe as in the forward kernel.
 template <typename T, bool MF>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256, 4)
 dual_fused_bwd_kernel(const StmCsr gft, const StmCsr gbt,
                       const T* __restrict__ xf, const T* pf1,
                       const T* __restrict__ xb, const T* pb1,
                       const T* __restrict__ dz, const T* __restrict__ W,
                       T* outf, T* outb, int N, int C, int Cout, int kofs_f,
-                      int kofs_b, float alpha, float beta, int final_step) {
+                      int kofs_b, float alpha, float beta, int final_step,
+                      int vec, int vec_dz) {
   const int b = blockIdx.y;
   const int n0 = blockIdx.x * GC_ST;
   extern __shared__ char lds[];
   float* utf = (float*)(lds + gc_slot_bytes(MF));
   float* utb = utf + GC_ST * 64;
+  const long boff = (long)b * N * C;
+
+  // ---- phase C's loads, first: the two gathers depend on neither dz, W nor
+  // U; one (row, 8-channel group) unit per thread, held in registers ----
+  const int G = C >> 3;
+  const int rl = threadIdx.x / (G > 0 ? G : 1), c = (threadIdx.x % (G > 0 ? G : 1)) * 8;
+  const int row = n0 + rl;
+  const bool live = vec && rl < GC_ST && row < N;
+  const long e8 = boff + (long)row * C + c;
+  float gf8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float gb8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  GcRaw8<T> rf = {}, rb = {};
+  if (live) {
+    if (pf1 != nullptr) rf = gc_load8<T>(&pf1[e8]);
+    if (pb1 != nullptr) rb = gc_load8<T>(&pb1[e8]);
+    if (xf != nullptr) gc_gather8<T>(gft, xf + boff, row, C, c, gf8);
+    if (xb != nullptr) gc_gather8<T>(gbt, xb + boff, row, C, c, gb8);
+  }
 
   // ---- phase A: stage the dz tile (once for both chains) ----
-  gc_stage_dz<T, MF>(lds, dz + (long)b * N * Cout, n0, N, Cout);
+  gc_stage_dz<T, MF>(lds, dz + (long)b * N * Cout, n0, N, Cout, vec_dz);
   __syncthreads();
 
   // ---- phase B: U_f (and U_b) = dz @ W_j^T ----
@@ -130,7 +201,44 @@ dual_fused_bwd_kernel(const StmCsr gft, const StmCsr gbt,
   __syncthreads();
 
   // ---- phase C: the two SpMM/axpby updates ----
-  const long boff = (long)b * N * C;
+  if (vec) {
+    if (!live) return;
+    const float4* uf = (const float4*)&utf[rl * 64 + c];
+    const float4 f0 = uf[0], f1 = uf[1];
+    float af[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+    float ab[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (!final_step) {
+      const float4* ub = (const float4*)&utb[rl * 64 + c];
+      const float4 b0 = ub[0], b1 = ub[1];
+      ab[0] = b0.x; ab[1] = b0.y; ab[2] = b0.z; ab[3] = b0.w;
+      ab[4] = b1.x; ab[5] = b1.y; ab[6] = b1.z; ab[7] = b1.w;
+    }
+    float pv[8];
+    #pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (xf != nullptr) af[q] = fmaf(alpha, gf8[q], af[q]);
+      if (xb != nullptr) ab[q] = fmaf(alpha, gb8[q], ab[q]);
+    }
+    if (pf1 != nullptr) {
+      gc_unpack8<T>(rf, pv);
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) af[q] = fmaf(beta, pv[q], af[q]);
+    }
+    if (pb1 != nullptr) {
+      gc_unpack8<T>(rb, pv);
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) ab[q] = fmaf(beta, pv[q], ab[q]);
+    }
+    if (final_step) {
+      #pragma unroll
+      for (int q = 0; q < 8; ++q) af[q] = stm_fadd(af[q], ab[q]);
+      gc_store8<T>(&outf[e8], af);
+    } else {
+      gc_store8<T>(&outf[e8], af);
+      gc_store8<T>(&outb[e8], ab);
+    }
+    return;
+  }
   for (int i = threadIdx.x; i < GC_ST * C; i += 256) {
     const int c = i % C, rl = i / C;
     const int row = n0 + rl;
@@ -163,7 +271,9 @@ void launch_dual_fwd(hipStream_t st, const DualFwdArgs& a) {
                        (const T*)a.pb1, (const T*)a.x0, (const T*)a.W,
                        (const T*)a.bias, (T*)a.pfout, (T*)a.pbout, a.yacc,
                        (T*)a.yout, a.N, a.C, a.Cout, a.kofs_f, a.kofs_b, a.alpha,
-                       a.beta, a.first, a.act);
+                       a.beta, a.first, a.act,
+                       (int)gc_vec8(a.N, a.C, {a.xf, a.pf1, a.xb, a.pb1, a.x0, a.pfout,
+                                          a.pbout}));
   });
 }
 
@@ -178,7 +288,9 @@ void launch_dual_bwd(hipStream_t st, const DualBwdArgs& a) {
                        (const T*)a.xf, (const T*)a.pf1, (const T*)a.xb,
                        (const T*)a.pb1, (const T*)a.dz, (const T*)a.W, (T*)a.outf,
                        (T*)a.outb, a.N, a.C, a.Cout, a.kofs_f, a.kofs_b, a.alpha,
-                       a.beta, a.final_step);
+                       a.beta, a.final_step,
+                       (int)gc_vec8(a.N, a.C, {a.xf, a.pf1, a.xb, a.pb1, a.outf, a.outb}),
+                       (int)gc_vec8(a.N, a.Cout, {a.dz}));
   });
 }
 

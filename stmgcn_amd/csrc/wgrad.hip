@@ -7,12 +7,16 @@
 // replace 15 library GEMM + 9 cat + 9 reduce launches per step with one
 // launch per RNN branch + one per graph-conv.
 //
-// Scheme per workgroup (256 threads, 4 waves): march a private chunk of the
-// reduction dim in 32-row K-tiles; stage A^T (and B^T) tiles in LDS with an
-// XOR swizzle that makes the 16B MFMA fragment reads bank-conflict-free;
-// accumulate the full output in registers (v_mfma_f32_16x16x32, fp32 acc);
-// one unsafeAtomicAdd(f32) per output element per workgroup at the end.
-// Bias grads (column sums) ride along in the staging pass for free.
+// Scheme per workgroup: march a private chunk of the reduction dim in 64-row
+// K-steps; stage the operands that need transposing as A^T / B^T tiles in LDS
+// with an XOR swizzle that makes the 16B MFMA fragment reads
+// bank-conflict-free; accumulate the full output in registers
+// (v_mfma_f32_16x16x32, fp32 acc); one unsafeAtomicAdd(f32) per output element
+// per workgroup at the end. Bias grads (column sums) ride along in the
+// staging pass for free. Both kernels run the same schedule: two named
+// register sets refilled two K-steps ahead (loop unrolled by two, no register
+// copies), double-buffered LDS tiles with one barrier per K-step, staging
+// loads in which consecutive lanes take consecutive 16-byte blocks of one row.
 //
 // LSTM variant reads the dA stream (L, Tst*S_pad, 4H) that lstm_bwd_kernel
 // writes in wgrad A-fragment tile order (common.h) — dA goes global ->
@@ -391,6 +395,14 @@ extern "C" void stmgcn_lstm_wgrad_grads(void* stream, int dtype, const void* dA,
 // (B,N,K_s,C) concat stack never exists). CA must be a multiple of 8 so
 // every 8-col fragment stays within one source.
 //
+// 256 threads, 4 waves; wave wv owns the m-tiles wv, wv + 4, .. (up to 4) and
+// all n-tiles. A K-step is 64 rows: its A^T [256][64] and B^T [64][64] tiles
+// (40 KiB) are double-buffered, 80 KiB of LDS, one workgroup per CU. Staging
+// unit = (row pair, 8-column block); a thread holds up to 4 A units and 1 B
+// unit per register set, two 16-byte loads each, committed as 4-byte
+// (row, row + 1) pairs. No scratch: accumulators and units are indexed at
+// compile time, the tile loops are predicated on the wave-uniform counts.
+//
 // FIN (the finishing form): the workgroup that draws the launch's last ticket
 // (stm_last_arriver, common.h) reads the <= 64 KiB of fp32 sums back and
 // writes dW (M, N) and db (N,) in the parameter dtype. C, db and the ticket
@@ -411,9 +423,12 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
                  float* __restrict__ C, float* __restrict__ db,
                  long rows, int M, int N, AtbFin<T> fin) {
   using frag = typename Frag8<T>::type;
-  extern __shared__ char lds[];
-  char* AT = lds;                  // [256][32] -> 16 KiB
-  char* BT = lds + 16384;         // [64][32]  ->  4 KiB
+  constexpr int KT = 64;                 // K-step rows
+  constexpr int AT_B = 256 * 2 * KT;     // A^T tile [256][KT], bytes
+  constexpr int BT_B = 64 * 2 * KT;      // B^T tile [64][KT]
+  constexpr int BUF_B = AT_B + BT_B;
+  constexpr int NUA = 4;                 // A units per thread: 32 pairs x 32 blocks / 256
+  extern __shared__ char lds[];          // 2 x (A^T | B^T)
   float* red = (float*)lds;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int l16 = lane & 15, lgrp = lane >> 4;
@@ -434,104 +449,143 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
   #pragma unroll
   for (int j = 0; j < 8; ++j) dbp[j] = 0.f;
 
-  // register-prefetch pipeline (same rationale as lstm_wgrad_kernel): A has
-  // up to 2 units/thread (unit u: pair pr = u & 15, col-block cb = u >> 4),
-  // B one unit for tid < 128
-  const int pr = threadIdx.x & 15;
-  const int cba = threadIdx.x >> 4, cba2 = cba + 16;  // A col-blocks
-  const int cbb = cba & 7;                            // B col-block (tid<128)
-  // resolve this thread's two col-blocks to (source tensor, column offset)
-  const T* Aa = nullptr;
-  const T* Ab = nullptr;
-  int oa = 0, ob = 0;
-  if (cba * 8 < M) { Aa = (const T*)As.a[(cba * 8) / CA]; oa = (cba * 8) % CA; }
-  if (cba2 * 8 < M) { Ab = (const T*)As.a[(cba2 * 8) / CA]; ob = (cba2 * 8) % CA; }
-  const frag fz = {};
-  frag va[2][2], vb[2];
-  auto load_tiles = [&](long kt, frag a[2][2], frag b[2]) {
-    const long ra = kt + pr * 2, rb = ra + 1;
-    a[0][0] = fz; a[0][1] = fz; a[1][0] = fz; a[1][1] = fz;
-    if (Aa != nullptr) {
-      if (ra < r1) a[0][0] = *(const frag*)&Aa[ra * CA + oa];
-      if (rb < r1) a[0][1] = *(const frag*)&Aa[rb * CA + oa];
-    }
-    if (Ab != nullptr) {
-      if (ra < r1) a[1][0] = *(const frag*)&Ab[ra * CA + ob];
-      if (rb < r1) a[1][1] = *(const frag*)&Ab[rb * CA + ob];
-    }
-    b[0] = fz; b[1] = fz;
-    if (threadIdx.x < 128 && cbb * 8 < N) {
-      if (ra < r1) b[0] = *(const frag*)&B[ra * N + cbb * 8];
-      if (rb < r1) b[1] = *(const frag*)&B[rb * N + cbb * 8];
-    }
-  };
-  auto commit_tiles = [&]() {
+  // Staging units of one K-step: (row pair p = 0..31, 8-column block cb). Unit
+  // u = p * ncb + cb, so consecutive lanes take the consecutive 16-byte blocks
+  // of one row (a source's CA columns are contiguous, then the next source's)
+  // and the row pairs spread over the lane groups. ncb counts the zero-padded
+  // blocks too (2 per 16-wide tile): a unit past M (or N) loads nothing and
+  // commits zeros. A thread's units are the same in every K-step, so their
+  // source, column and row pair are resolved once, here.
+  const int ncba = mtiles * 2, ncbb = ntiles * 2;
+  const T* ap[NUA];      // source + column offset, null: no such unit / padding
+  int apair[NUA], acb[NUA];
+  #pragma unroll
+  for (int i = 0; i < NUA; ++i) {
+    const int u = threadIdx.x + i * 256;
+    apair[i] = u / ncba; acb[i] = u % ncba;
+    ap[i] = nullptr;
+    if (u < 32 * ncba && acb[i] * 8 < M)
+      ap[i] = (const T*)As.a[(acb[i] * 8) / CA] + (acb[i] * 8) % CA;
+  }
+  const int bpair = threadIdx.x / ncbb, bcb = threadIdx.x % ncbb;
+  const bool bunit = threadIdx.x < 32 * ncbb;       // commits (zeros past N)
+  const T* bp = (bunit && bcb * 8 < N) ? B + bcb * 8 : nullptr;
+
+  struct Regs { frag a[NUA][2]; frag b[2]; };
+  auto load_tiles = [&](long kt, Regs& g) {
+    const frag fz = {};
     #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int cb = (u == 0) ? cba : cba2;
-      #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        union { T t2[2]; int i; } pk;
-        pk.t2[0] = ((const T*)&va[u][0])[j];
-        pk.t2[1] = ((const T*)&va[u][1])[j];
-        *(int*)&AT[tswz<64>(cb * 8 + j, pr * 4)] = pk.i;
+    for (int i = 0; i < NUA; ++i) {
+      g.a[i][0] = fz; g.a[i][1] = fz;
+      const long ra = kt + apair[i] * 2;
+      if (ap[i] != nullptr) {
+        if (ra < r1) g.a[i][0] = *(const frag*)&ap[i][ra * CA];
+        if (ra + 1 < r1) g.a[i][1] = *(const frag*)&ap[i][(ra + 1) * CA];
       }
     }
-    if (threadIdx.x < 128) {
+    g.b[0] = fz; g.b[1] = fz;
+    const long rb = kt + bpair * 2;
+    if (bp != nullptr) {
+      if (rb < r1) g.b[0] = *(const frag*)&bp[rb * N];
+      if (rb + 1 < r1) g.b[1] = *(const frag*)&bp[(rb + 1) * N];
+    }
+  };
+  auto commit_tiles = [&](char* buf, const Regs& g) {
+    char* AT = buf;
+    char* BT = buf + AT_B;
+    #pragma unroll
+    for (int i = 0; i < NUA; ++i) {
+      if (threadIdx.x + i * 256 < 32 * ncba) {
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          union { T t2[2]; int i; } pk;
+          pk.t2[0] = ((const T*)&g.a[i][0])[j];
+          pk.t2[1] = ((const T*)&g.a[i][1])[j];
+          *(int*)&AT[tswz<2 * KT>(acb[i] * 8 + j, apair[i] * 4)] = pk.i;
+        }
+      }
+    }
+    if (bunit) {
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
         union { T t2[2]; int i; } pk;
-        pk.t2[0] = ((const T*)&vb[0])[j];
-        pk.t2[1] = ((const T*)&vb[1])[j];
-        *(int*)&BT[tswz<64>(cbb * 8 + j, pr * 4)] = pk.i;
+        pk.t2[0] = ((const T*)&g.b[0])[j];
+        pk.t2[1] = ((const T*)&g.b[1])[j];
+        *(int*)&BT[tswz<2 * KT>(bcb * 8 + j, bpair * 4)] = pk.i;
         if (db) dbp[j] += toF<T>(pk.t2[0]) + toF<T>(pk.t2[1]);
       }
     }
   };
 
-  load_tiles(r0, va, vb);
-  for (long kt = r0; kt < r1; kt += 32) {
-    commit_tiles();
+  // One K-step on register set g and LDS buffer buf: the set is refilled for
+  // the step TWO ahead as soon as it has been committed, and the two sets
+  // alternate by name (loop unrolled by 2), so there is no register copy and
+  // every load has a whole K-step in flight before its first use (same scheme
+  // as lstm_wgrad_kernel). The LDS tiles are double-buffered: one barrier per
+  // K-step (the commit of step k+2 into the buffer step k read is ordered
+  // behind barrier k+1, which every wave reaches only after its step-k
+  // MFMAs). Past the chunk end the loads issue nothing and leave zeros. The
+  // tile loops are fully unrolled and predicated (wave-uniform), so acc is
+  // indexed at compile time and a wave skips the m- and n-tiles M and N do
+  // not reach (M = 24, N = 8: two waves run one MFMA pair per K-half).
+  auto kstep = [&](long kt, char* buf, Regs& g) {
+    commit_tiles(buf, g);
+    load_tiles(kt + 2 * KT, g);
     __syncthreads();
-    frag na[2][2], nb[2];
-    const bool more = kt + 32 < r1;
-    if (more) load_tiles(kt + 32, na, nb);
-    for (int i = 0; i < mt_mine; ++i) {
-      const int mt = wv + i * 4;
-      const frag a = frag_from<T, 64>(AT, mt * 16 + l16, lgrp * 16);
-      for (int nt = 0; nt < ntiles; ++nt)
-        acc[i][nt] = mfma16x16x32(a, frag_from<T, 64>(BT, nt * 16 + l16, lgrp * 16),
-                                  acc[i][nt]);
+    const char* AT = buf;
+    const char* BT = buf + AT_B;
+    #pragma unroll
+    for (int kh = 0; kh < 2; ++kh) {
+      const int koff = kh * KT + lgrp * 16;   // byte offset of the K half
+      frag bf[4];
+      #pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+        if (nt < ntiles) bf[nt] = frag_from<T, 2 * KT>(BT, nt * 16 + l16, koff);
+      #pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (i < mt_mine) {
+          const frag a = frag_from<T, 2 * KT>(AT, (wv + i * 4) * 16 + l16, koff);
+          #pragma unroll
+          for (int nt = 0; nt < 4; ++nt)
+            if (nt < ntiles) acc[i][nt] = mfma16x16x32(a, bf[nt], acc[i][nt]);
+        }
+      }
     }
-    __syncthreads();
-    if (more) {
-      va[0][0] = na[0][0]; va[0][1] = na[0][1];
-      va[1][0] = na[1][0]; va[1][1] = na[1][1];
-      vb[0] = nb[0]; vb[1] = nb[1];
-    }
-  }
+  };
 
-  for (int i = 0; i < mt_mine; ++i) {
+  Regs g0, g1;
+  load_tiles(r0, g0);
+  load_tiles(r0 + KT, g1);
+  for (long kt = r0; kt < r1; kt += 2 * KT) {
+    kstep(kt, lds, g0);
+    if (kt + KT < r1) kstep(kt + KT, lds + BUF_B, g1);   // WG-uniform
+  }
+  __syncthreads();   // red (and the ticket flag) reuse the tiles' LDS
+
+  #pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (i >= mt_mine) continue;
     const int mt = wv + i * 4;
-    for (int nt = 0; nt < ntiles; ++nt)
+    #pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      if (nt >= ntiles) continue;
       #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int m = mt * 16 + lgrp * 4 + rr, n = nt * 16 + l16;
         if (m < M && n < N) unsafeAtomicAdd(&C[(long)m * N + n], acc[i][nt][rr]);
       }
+    }
   }
 
   if (db) {
-    // B-staging thread tid < 128 held col-block tid >> 4
+    // B-staging thread tid < 32 * ncbb held column block tid % ncbb
     #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      red[threadIdx.x * 8 + j] = (threadIdx.x < 128) ? dbp[j] : 0.f;
+    for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = bunit ? dbp[j] : 0.f;
     __syncthreads();
-    if (threadIdx.x < 64 && threadIdx.x < N) {
+    if (threadIdx.x < N) {
       const int n = threadIdx.x, cb = n >> 3, j = n & 7;
       float v = 0.f;
-      #pragma unroll
-      for (int k = 0; k < 16; ++k) v += red[(cb * 16 + k) * 8 + j];
+      for (int k = 0; k < 32; ++k) v += red[(k * ncbb + cb) * 8 + j];
       unsafeAtomicAdd(&db[n], v);
     }
   }
@@ -562,12 +616,16 @@ static void atb_wgrad_launch(void* stream, int dtype, const void** As,
                              int nsrc, int CA, const void* B, float* C,
                              float* db, long rows, int N, unsigned* fin_ticket,
                              void* fin_dW, void* fin_db) {
-  // fill the 256-CU chip: ~128 rows per workgroup minimum (4 K-tiles)
-  long nchunks = (rows + 127) / 128;
+  // 256 rows (four K-steps) per workgroup, at most 512 workgroups. At the
+  // flagship shape (32768 rows, M = 192, N = 64) that is 128 workgroups and
+  // 6.3 MB of float atomics; 128 rows (256 workgroups, twice the atomics) and
+  // 512 rows (64 workgroups streaming) both measured slower, in isolation and
+  // in the step (profiles/gconv_vector_tiles.md).
+  long nchunks = (rows + 255) / 256;
   if (nchunks > 512) nchunks = 512;
   if (nchunks < 1) nchunks = 1;
   const dim3 grid((unsigned)nchunks), blk(256);
-  const size_t lds = 16384 + 4096;
+  const size_t lds = 2 * (256 + 64) * 128;   // double-buffered A^T | B^T, 64-row steps
   const int M = nsrc * CA;
   AtbSrc src{};
   for (int i = 0; i < nsrc && i < 4; ++i) src.a[i] = As[i];
@@ -575,6 +633,9 @@ static void atb_wgrad_launch(void* stream, int dtype, const void** As,
     using T = decltype(t);
     const AtbFin<T> fin{fin_ticket, (T*)fin_dW, (T*)fin_db};
     stm_dispatch_bool(fin_ticket != nullptr, [&](auto finc) {
+      STM_CHECK_HIP(hipFuncSetAttribute(
+          (const void*)atb_wgrad_kernel<T, decltype(finc)::value>,
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL((atb_wgrad_kernel<T, decltype(finc)::value>), grid, blk,
                          lds, (hipStream_t)stream, src, CA, (const T*)B, C, db,
                          rows, M, N, fin);
