@@ -41,8 +41,7 @@ def bench_lstm_wgrad(C):
     us = timeit(lambda: C.lstm_wgrad(dA, hseq, x))
     gb = (dA.numel() + hseq.numel() + x.numel()) * 2 / 1e9
     print(json.dumps({"kernel": "lstm_wgrad", "us": round(us, 1),
-                      "eff_tb_s": round(gb / (us * 1e-6) / 1e3, 2),
-                      "chunks": os.environ.get("STMGCN_WGRAD_CHUNKS", "auto")}))
+                      "eff_tb_s": round(gb / (us * 1e-6) / 1e3, 2)}))
 
 
 def bench_atb(C):

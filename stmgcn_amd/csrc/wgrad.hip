@@ -13,10 +13,14 @@
 // bank-conflict-free; accumulate the full output in registers
 // (v_mfma_f32_16x16x32, fp32 acc); one unsafeAtomicAdd(f32) per output element
 // per workgroup at the end. Bias grads (column sums) ride along in the
-// staging pass for free. Both kernels run the same schedule: two named
-// register sets refilled two K-steps ahead (loop unrolled by two, no register
-// copies), double-buffered LDS tiles with one barrier per K-step, staging
-// loads in which consecutive lanes take consecutive 16-byte blocks of one row.
+// staging pass for free. Both kernels keep two named register sets (loop
+// unrolled by two, no register copies), double-buffered LDS tiles with one
+// barrier per K-step, and staging loads in which consecutive lanes take
+// consecutive 16-byte blocks of one row. lstm_wgrad_kernel's loads are
+// branch-free (clamped address, value selected at its use), so its waits are
+// counted and two K-steps of loads stay in flight; atb_wgrad_kernel's loads
+// are guarded, and the compiler drains the queue at every K-step there (the
+// branch-free form measured no faster: profiles/wgrad_load_pipeline.md).
 //
 // LSTM variant reads the dA stream (L, Tst*S_pad, 4H) that lstm_bwd_kernel
 // writes in wgrad A-fragment tile order (common.h) — dA goes global ->
@@ -48,6 +52,16 @@ __device__ __forceinline__ typename Frag8<T>::type frag_from(
   return *(const typename Frag8<T>::type*)&lds_tile[tswz<RB>(g, koff_bytes)];
 }
 
+// The layer forms of lstm_wgrad_kernel, dispatched once per workgroup: f gets
+// the form as a std::integral_constant, so no stage holds another form's code.
+enum : int { WG_SCALAR0 = 0, WG_DENSE0 = 1, WG_HANDOFF = 2 };
+template <typename F>
+__device__ __forceinline__ void wgrad_uniform_form(int form, F&& f) {
+  if (form == WG_SCALAR0) f(std::integral_constant<int, WG_SCALAR0>{});
+  else if (form == WG_DENSE0) f(std::integral_constant<int, WG_DENSE0>{});
+  else f(std::integral_constant<int, WG_HANDOFF>{});
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -72,12 +86,14 @@ __device__ __forceinline__ typename Frag8<T>::type frag_from(
 //
 // Every wave owns 32 gate rows (2 m-tiles), so the 8 waves of a 512-thread
 // workgroup consume whole dA rows and hp/hx are staged once. One launch
-// serves every layer, layer = blockIdx.y (cin1 != 0: layer 0 reads the scalar
-// input x and only column 0 of its dw_ih is live). A 256-thread gate-split
-// form and a separate single-column launch for that layer 0 both measured
-// slower (profiles/r03_da_stream_layout.md). Chunks are whole tiles (tpc per
-// workgroup); an odd tile count leaves the second half of the last K-step
-// zero.
+// serves every layer, layer = blockIdx.y, in one of three workgroup-uniform
+// forms with a straight-line K loop each: scalar-input layer 0 (cin1 != 0:
+// x is (S, Tst, 1) and only column 0 of its dw_ih is live), dense layer 0,
+// and hand-off layer (layer > 0 reads hseq[layer - 1]). A 256-thread
+// gate-split form and a separate single-column launch for that layer 0 both
+// measured slower (profiles/r03_da_stream_layout.md). Chunks are whole tiles
+// (tpc per workgroup); the pair loop always runs both of its K-steps, and a
+// K-step or K-half past the chunk end adds zeros.
 //
 // FIN (the finishing form): after its atomics every workgroup arrives at its
 // layer's ticket (stm_last_arriver, common.h); the last one of a layer reads
@@ -147,113 +163,176 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   // x 8 column blocks): row pair p sits at k' = 2p, 2p+1 of K-half p >> 4,
   // i.e. tile rows rho(2(p&15)) and the next one (rho keeps even/odd k' pairs
   // adjacent). 8 consecutive lanes take the 8 column blocks of one row: 128 B
-  // coalesced. Threads 0..255 stage hp, 256..511 stage hx.
+  // coalesced. Threads 0..255 (waves 0..3) stage hp, 256..511 stage hx.
   const int scb = threadIdx.x & 7, sp = (threadIdx.x >> 3) & 31;
   const int skh = sp >> 4, srow = stm_da_rho(2 * (sp & 15));
-  const int sop = threadIdx.x >> 8;
+  const bool sop = threadIdx.x >= 256;
 
-  auto load_h = [&](long tb, frag v[2]) {
-    const frag fz = {};
-    const long tile = tb + skh;
-    const long r = tile * SEQ_TILE + srow;     // rows r, r + 1 (same tile)
-    v[0] = fz; v[1] = fz;
-    if (tile >= tb1) return;
-    if (sop == 0) {
-      // h_{t-1}: hseq[l] offset -S_pad rows, zero for t==0 (the guard must
-      // gate the LOAD — for layer 0, r - S_pad points before the allocation)
-      if (tile >= tp0) {
-        v[0] = *(const frag*)&hp_l[(r - S_pad) * 64 + scb * 8];
-        v[1] = *(const frag*)&hp_l[(r + 1 - S_pad) * 64 + scb * 8];
-      }
-    } else if (!l0) {
-      v[0] = *(const frag*)&hx_l[r * 64 + scb * 8];
-      v[1] = *(const frag*)&hx_l[(r + 1) * 64 + scb * 8];
-    } else {
-      const long s_ = r % S_pad, t_ = r / S_pad;   // pad rows (s >= S) stay 0
-      if (x1) {
-        if (scb == 0) {
-          if (s_ < S) ((T*)&v[0])[0] = x[s_ * Tst + t_];
-          if (s_ + 1 < S) ((T*)&v[1])[0] = x[(s_ + 1) * Tst + t_];
-        }
-      } else {
-        if (s_ < S) v[0] = *(const frag*)&x[(s_ * Tst + t_) * 64 + scb * 8];
-        if (s_ + 1 < S)
-          v[1] = *(const frag*)&x[((s_ + 1) * Tst + t_) * 64 + scb * 8];
-      }
-    }
+  // Register set of one K-step. No load stands under a branch: a row that
+  // must read as zero (past the chunk end, t == 0 for h_{t-1}, a pad row
+  // s >= S of x) is loaded from the first element of its own tensor instead
+  // -- the ADDRESS is selected, so nothing outside the tensor is touched, and
+  // every lane of a dead wave-load hits one line -- and the VALUE is selected
+  // against zero where it is used (`live`; a select, so whatever the dead
+  // address holds, NaN included, never reaches a sum). With every path
+  // issuing the same loads the compiler counts its waits instead of
+  // draining the queue at each join.
+  struct KSet {
+    frag h[2];                // rows r, r + 1 of hp (waves 0..3) or hx (4..7)
+    unsigned short xs[2];     // scalar-input form: the two x values
+    frag a[2][MTG];           // dA A-fragments [K-half = tile][m-tile]
+    int live;                 // bit i: h[i] / xs[i] is a real row
   };
-  auto commit_h = [&](char* buf, const frag v[2]) {
-    char* tileT = buf + sop * HT;
+
+  auto load_h = [&](auto form, long tb, KSet& g) {
+    constexpr int F = decltype(form)::value;
+    const long tile = tb + skh;
+    const bool tin = tile < tb1;
+    const long r = tile * SEQ_TILE + srow;     // rows r, r + 1 (same tile)
+    // h_{t-1}: hseq[l] offset -S_pad rows; t == 0 has none (for layer 0,
+    // r - S_pad would point before the allocation)
+    const bool hlive = tin && tile >= tp0 && !(F == WG_SCALAR0 && sop);
+    const T* ph = hlive ? hp_l + (r - S_pad) * 64 : hp_l;
+    const T *p0 = ph, *p1 = ph + 64;
+    bool lv0 = hlive, lv1 = hlive;
+    if constexpr (F == WG_HANDOFF) {
+      const T* px = tin ? hx_l + r * 64 : hx_l;
+      p0 = sop ? px : p0; p1 = sop ? px + 64 : p1;
+      lv0 = lv1 = sop ? tin : hlive;
+    } else {
+      // layer 0 reads x (S, Tst, cin): t = tile / tp0, pad rows s >= S are dead
+      const long t_ = (unsigned)tile / (unsigned)tp0;
+      const long s_ = r - t_ * S_pad;
+      const bool x0 = sop && tin && s_ < S, x1 = sop && tin && s_ + 1 < S;
+      const long e0 = x0 ? s_ * Tst + t_ : 0, e1 = x1 ? (s_ + 1) * Tst + t_ : 0;
+      if constexpr (F == WG_DENSE0) {
+        p0 = sop ? x + e0 * 64 : p0; p1 = sop ? x + e1 * 64 : p1;
+      } else {
+        // Every wave issues both kinds of load, so the queue holds the same
+        // count on every path: waves 4..7 take their x values here and send
+        // their two fragment loads to the first row of hp, waves 0..3 send
+        // these two to x[0]; the dead ones hit one line per wave.
+        g.xs[0] = *(const unsigned short*)&x[e0];
+        g.xs[1] = *(const unsigned short*)&x[e1];
+      }
+      lv0 = sop ? x0 : hlive; lv1 = sop ? x1 : hlive;
+    }
+    g.h[0] = *(const frag*)&p0[scb * 8];
+    g.h[1] = *(const frag*)&p1[scb * 8];
+    g.live = (lv0 ? 1 : 0) | (lv1 ? 2 : 0);
+  };
+  auto commit_h = [&](auto form, char* buf, const KSet& g) {
+    constexpr int F = decltype(form)::value;
+    const frag fz = {};
+    char* tileT = buf + (sop ? HT : 0);
+    const frag v0 = (g.live & 1) ? g.h[0] : fz;
+    const frag v1 = (g.live & 2) ? g.h[1] : fz;
+    // scalar input: the hx fragment is built here, only column 0 is live
+    const int xw = ((g.live & 1) ? (int)g.xs[0] : 0) |
+                   ((g.live & 2) ? (int)g.xs[1] << 16 : 0);
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      union { T t2[2]; int i; } pk;
-      pk.t2[0] = ((const T*)&v[0])[j];
-      pk.t2[1] = ((const T*)&v[1])[j];
-      *(int*)&tileT[tswz<2 * KT>(scb * 8 + j, sp * 4)] = pk.i;
+      union { typename Frag8<T>::elem t2[2]; int i; } pk;
+      pk.t2[0] = v0[j];
+      pk.t2[1] = v1[j];
+      int w = pk.i;
+      if constexpr (F == WG_SCALAR0) w = sop ? ((j == 0 && scb == 0) ? xw : 0) : w;
+      *(int*)&tileT[tswz<2 * KT>(scb * 8 + j, sp * 4)] = w;
     }
   };
-  // dA A-fragments of one K-step: [K-half = tile][m-tile]
-  auto load_a = [&](long tb, frag a[2][MTG]) {
-    const frag fz = {};
+  auto load_a = [&](long tb, KSet& g) {
     #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
       #pragma unroll
       for (int mt = 0; mt < MTG; ++mt) {
-        a[kh][mt] = fz;
-        if (tb + kh < tb1)
-          a[kh][mt] = *(const frag*)&dA_l[stm_da_tile_off((tb + kh) * SEQ_TILE) +
-                                          stm_da_elem(gw + mt * 16 + l16, 8 * lgrp)];
+        const long off = stm_da_tile_off((tb + kh) * SEQ_TILE) +
+                         stm_da_elem(gw + mt * 16 + l16, 8 * lgrp);
+        g.a[kh][mt] = *(const frag*)&dA_l[tb + kh < tb1 ? off : 0];
       }
   };
 
-  // One K-step on register set (vs, a) and LDS buffer buf. The set is
-  // refilled for the step TWO ahead as soon as it has been consumed, so
-  // every load has a whole K-step in flight before its first use, and the
-  // two sets alternate by name (loop unrolled by 2): no register copies, so
-  // no wait on a load that was only just issued. Past the chunk end the
-  // loads issue nothing and leave zeros.
-  auto kstep = [&](long tb, char* buf, frag vs[2], frag a[2][MTG]) {
+  // One K-step on register set g and LDS buffer buf, in this issue order:
+  //   commit h(k) -> request h(k+2) -> barrier -> fragment reads and MFMAs on
+  //   dA(k) -> request dA(k+2).
+  // The set is refilled for the step TWO ahead as soon as each half has been
+  // consumed, and the two sets alternate by name (loop unrolled by 2, no
+  // register copies). With 2 h and 4 dA loads per thread per K-step the waits
+  // before the commit are vmcnt(11) and (10): dA(k), h(k+1), dA(k+1) stay in
+  // flight; the waits before the MFMAs on dA(k) run from vmcnt(11) to (8):
+  // h(k+1), dA(k+1), h(k+2) stay in flight (13/12 and 15..12 in the
+  // scalar-input form with its 4 h loads). No vmcnt(0) inside the loop: a CU
+  // keeps two K-steps of 48 KB under way. The scheduling barriers pin the
+  // commit, the two request points and the fragment-read groups.
+  auto kstep = [&](auto form, long tb, char* buf, KSet& g) {
     char* hpT = buf;
     char* hxT = buf + HT;
-    commit_h(buf, vs);
-    load_h(tb + 4, vs);
+    commit_h(form, buf, g);
+    __builtin_amdgcn_sched_barrier(0);
+    load_h(form, tb + 4, g);
+    __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
+    // Fragment reads run half a K-half ahead of their MFMAs: bh(1) is read
+    // behind the hh MFMAs of half 0 and bx(1) behind its ih MFMAs, so at most
+    // three of the four 16-register fragment groups are live at once. Every
+    // accumulator still takes its products in the order kh = 0, 1.
+    const frag fz = {};
+    frag bh[2][4], bx[2][4], af[2][MTG];
+    auto read_b = [&](frag (&b)[4], const char* tileT, int kh) {
+      #pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+        b[nt] = frag_from<T, 2 * KT>(tileT, nt * 16 + l16, kh * KT + lgrp * 16);
+    };
+    auto mfma_b = [&](f32x4 (&acc)[MTG][4], const frag (&b)[4], int kh) {
+      #pragma unroll
+      for (int mt = 0; mt < MTG; ++mt)
+        #pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+          acc[mt][nt] = mfma16x16x32(af[kh][mt], b[nt], acc[mt][nt]);
+    };
     #pragma unroll
-    for (int kh = 0; kh < 2; ++kh) {
-      const int koff = kh * KT + lgrp * 16;   // byte offset of the K half
-      frag bh[4], bx[4];
+    for (int kh = 0; kh < 2; ++kh)
       #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) bh[nt] = frag_from<T, 2 * KT>(hpT, nt * 16 + l16, koff);
-      #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) bx[nt] = frag_from<T, 2 * KT>(hxT, nt * 16 + l16, koff);
+      for (int mt = 0; mt < MTG; ++mt)   // past the chunk end: adds zeros
+        af[kh][mt] = tb + kh < tb1 ? g.a[kh][mt] : fz;
+    read_b(bh[0], hpT, 0);
+    read_b(bx[0], hxT, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_b(acc_hh, bh[0], 0);
+    read_b(bh[1], hpT, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_b(acc_ih, bx[0], 0);
+    read_b(bx[1], hxT, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_b(acc_hh, bh[1], 1);
+    mfma_b(acc_ih, bx[1], 1);
+    #pragma unroll
+    for (int kh = 0; kh < 2; ++kh)
       #pragma unroll
       for (int mt = 0; mt < MTG; ++mt) {
-        const frag af = a[kh][mt];
-        #pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          acc_hh[mt][nt] = mfma16x16x32(af, bh[nt], acc_hh[mt][nt]);
-        #pragma unroll
-        for (int nt = 0; nt < 4; ++nt)
-          acc_ih[mt][nt] = mfma16x16x32(af, bx[nt], acc_ih[mt][nt]);
         float sa = 0.f;
         #pragma unroll
-        for (int j = 0; j < 8; ++j) sa += (float)af[j];
+        for (int j = 0; j < 8; ++j) sa += (float)af[kh][mt][j];
         dbp[mt] += sa;
       }
-    }
-    load_a(tb + 4, a);
+    __builtin_amdgcn_sched_barrier(0);
+    load_a(tb + 4, g);
   };
 
-  frag vs0[2], vs1[2], a0[2][MTG], a1[2][MTG];
-  load_h(tb0, vs0);
-  load_a(tb0, a0);
-  load_h(tb0 + 2, vs1);
-  load_a(tb0 + 2, a1);
-  for (long tb = tb0; tb < tb1; tb += 4) {
-    kstep(tb, lds, vs0, a0);
-    if (tb + 2 < tb1) kstep(tb + 2, lds + 2 * HT, vs1, a1);   // WG-uniform
-  }
-
+  // One straight-line loop per workgroup-uniform layer form; the pair loop
+  // runs both K-steps unconditionally (a K-step past the end adds zeros).
+  wgrad_uniform_form(l0 ? (cin1 ? WG_SCALAR0 : WG_DENSE0) : WG_HANDOFF, [&](auto form) {
+    KSet g0, g1;
+    load_h(form, tb0, g0);
+    load_a(tb0, g0);
+    load_h(form, tb0 + 2, g1);
+    load_a(tb0 + 2, g1);
+    long tb = tb0;
+    do {   // an empty chunk (finishing form only) runs one pair of zeros
+      kstep(form, tb, lds, g0);
+      kstep(form, tb + 2, lds + 2 * HT, g1);
+      tb += 4;
+    } while (tb < tb1);
+  });
 
   // ---- writeback: one f32 atomic per output element per workgroup --------
   float* whh = dwhh + (long)layer * 256 * 64;
@@ -333,18 +412,21 @@ static void lstm_wgrad_launch(void* stream, int dtype, const void* dA,
                               float* dwhh, float* db, long R, long S_pad,
                               int S, int Tst, int L, int cin,
                               unsigned* tickets, void* out, int gru) {
-  static long env_chunks = -1;   // STMGCN_WGRAD_CHUNKS: perf experiments
-  if (env_chunks < 0) {
-    const char* e = getenv("STMGCN_WGRAD_CHUNKS");
-    env_chunks = e ? atol(e) : 0;
-  }
   if (R <= 0 || R % SEQ_TILE != 0) {
     printf("stmgcn_lstm_wgrad: R=%ld is not a whole number of dA tiles\n", R);
     return;
   }
-  // chunks are whole 32-row tiles of the tiled dA stream
+  // Chunks are whole 32-row tiles of the tiled dA stream: at most one per
+  // 1024 rows, and at most 256 / L per layer, i.e. one workgroup per CU in a
+  // single round. Two rounds of half-length chunks (512 / L) measured slower,
+  // alone and in the step (profiles/wgrad_load_pipeline.md): twice the
+  // prologues, dead prefetches and atomics for the same stream.
   const long ntile = R / SEQ_TILE;
-  const long target = env_chunks > 0 ? env_chunks : 512 / (L > 0 ? L : 1);
+  if (ntile >= (1L << 31)) {
+    printf("stmgcn_lstm_wgrad: R=%ld has too many dA tiles\n", R);
+    return;
+  }
+  const long target = 256 / (L > 0 ? L : 1);
   long nchunks = (R + 1023) / 1024;
   if (nchunks > target) nchunks = target;
   if (nchunks < 1) nchunks = 1;
@@ -519,15 +601,21 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
 
   // One K-step on register set g and LDS buffer buf: the set is refilled for
   // the step TWO ahead as soon as it has been committed, and the two sets
-  // alternate by name (loop unrolled by 2), so there is no register copy and
-  // every load has a whole K-step in flight before its first use (same scheme
-  // as lstm_wgrad_kernel). The LDS tiles are double-buffered: one barrier per
-  // K-step (the commit of step k+2 into the buffer step k read is ordered
-  // behind barrier k+1, which every wave reaches only after its step-k
-  // MFMAs). Past the chunk end the loads issue nothing and leave zeros. The
-  // tile loops are fully unrolled and predicated (wave-uniform), so acc is
-  // indexed at compile time and a wave skips the m- and n-tiles M and N do
-  // not reach (M = 24, N = 8: two waves run one MFMA pair per K-half).
+  // alternate by name (loop unrolled by 2, no register copy). The loads stand
+  // under their guards (unit, row end, second step of the pair), so at each
+  // join the compiler waits vmcnt(0): a commit drains the queue, the refill
+  // issued just before it included, and one K-step of loads is in flight at
+  // a time. With four K-steps per workgroup the prologue, the atomics and
+  // the finishing tail dominate; the branch-free form with counted waits
+  // (lstm_wgrad_kernel's) measured no faster here and was not kept
+  // (profiles/wgrad_load_pipeline.md). The LDS tiles are double-buffered: one
+  // barrier per K-step (the commit of step k+2 into the buffer step k read is
+  // ordered behind barrier k+1, which every wave reaches only after its
+  // step-k MFMAs). Past the chunk end the loads issue nothing and leave
+  // zeros. The tile loops are fully unrolled and predicated (wave-uniform),
+  // so acc is indexed at compile time and a wave skips the m- and n-tiles M
+  // and N do not reach (M = 24, N = 8: two waves run one MFMA pair per
+  // K-half).
   auto kstep = [&](long kt, char* buf, Regs& g) {
     commit_tiles(buf, g);
     load_tiles(kt + 2 * KT, g);
