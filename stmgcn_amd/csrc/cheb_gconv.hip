@@ -264,8 +264,8 @@ cheb_fused_bwd_kernel(const int* __restrict__ rowptr,
 // MFMA epilogue when the mix runs (W != null) and gc_fwd_mfma serves the
 // widths, scalar kernel otherwise. LDS: the tile slot (+ the x0 slot).
 template <typename T>
-void launch_fused_fwd(hipStream_t st, const ChebFwdArgs& a) {
-  gc_dispatch_mf<T>(a.W != nullptr && gc_fwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
+const char* launch_fused_fwd(hipStream_t st, const ChebFwdArgs& a) {
+  return gc_dispatch_mf<T>(a.W != nullptr && gc_fwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
     constexpr bool MF = decltype(mf)::value;
     hipLaunchKernelGGL((cheb_fused_fwd_kernel<T, MF>), gc_grid(a.N, a.B), dim3(256),
                        (a.x0 ? 2 : 1) * gc_slot_bytes(MF), st, a.g.rowptr,
@@ -273,13 +273,14 @@ void launch_fused_fwd(hipStream_t st, const ChebFwdArgs& a) {
                        (const T*)a.x0, (const T*)a.W, (const T*)a.bias, (T*)a.pout,
                        a.yacc, (T*)a.yout, a.N, a.C, a.Cout, a.kofs, a.alpha, a.beta,
                        a.first, a.act, (int)gc_vec8(a.N, a.C, {a.xin, a.p1, a.x0, a.pout}));
+    return stm_launched();
   });
 }
 
 // MFMA U GEMM when gc_bwd_mfma serves the widths. LDS: dz slot + one fp32 U tile.
 template <typename T>
-void launch_fused_bwd(hipStream_t st, const ChebBwdArgs& a) {
-  gc_dispatch_mf<T>(gc_bwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
+const char* launch_fused_bwd(hipStream_t st, const ChebBwdArgs& a) {
+  return gc_dispatch_mf<T>(gc_bwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
     constexpr bool MF = decltype(mf)::value;
     hipLaunchKernelGGL((cheb_fused_bwd_kernel<T, MF>), gc_grid(a.N, a.B), dim3(256),
                        gc_slot_bytes(MF) + GC_F32_TILE_BYTES, st, a.g.rowptr,
@@ -288,40 +289,40 @@ void launch_fused_bwd(hipStream_t st, const ChebBwdArgs& a) {
                        a.kofs, a.alpha, a.beta,
                        (int)gc_vec8(a.N, a.C, {a.xin, a.p1, a.out}),
                        (int)gc_vec8(a.N, a.Cout, {a.dz}));
+    return stm_launched();
   });
 }
 
 }  // namespace
 
-extern "C" void stmgcn_spmm_step(
-    void* stream_v, int dtype, const int* rowptr, const int* colidx,
-    const float* vals, const void* xin, const void* p1, const void* p2,
-    void* out, int B, int N, int C,
-    long sx, long s1, long s2, long so,
-    long bx, long b1, long b2, long bo,
-    float alpha, float beta, float gamma) {
+extern "C" const char* stmgcn_spmm_step(void* stream_v, int dtype, const SpmmArgs& a) {
+  const int C = a.C;
   const int rows_per_block = (C <= 256) ? (256 / C > 0 ? 256 / C : 1) : 1;
-  const dim3 grid((N + rows_per_block - 1) / rows_per_block, B);
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  const dim3 grid((a.N + rows_per_block - 1) / rows_per_block, a.B);
+  return stm_dispatch_dtype("stmgcn_spmm_step: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL((spmm_step_kernel<T>), grid, dim3(256), 0,
-                       (hipStream_t)stream_v, rowptr, colidx, vals,
-                       (const T*)xin, (const T*)p1, (const T*)p2, (T*)out,
-                       N, C, rows_per_block, sx, s1, s2, so, bx, b1, b2, bo,
-                       alpha, beta, gamma);
+                       (hipStream_t)stream_v, a.g.rowptr, a.g.colidx, a.g.vals,
+                       (const T*)a.xin.ptr, (const T*)a.p1.ptr, (const T*)a.p2.ptr,
+                       (T*)const_cast<void*>(a.out.ptr), a.N, C, rows_per_block,
+                       a.xin.srow, a.p1.srow, a.p2.srow, a.out.srow, a.xin.sbatch,
+                       a.p1.sbatch, a.p2.sbatch, a.out.sbatch, a.alpha, a.beta, a.gamma);
+    return stm_launched();
   });
 }
 
-extern "C" void stmgcn_cheb_fused_fwd_step(void* stream_v, int dtype,
-                                           const ChebFwdArgs& a) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
-    launch_fused_fwd<decltype(t)>((hipStream_t)stream_v, a);
+extern "C" const char* stmgcn_cheb_fused_fwd_step(void* stream_v, int dtype,
+                                                  const ChebFwdArgs& a) {
+  return stm_dispatch_dtype("stmgcn_cheb_fused_fwd_step: unsupported dtype code", dtype,
+                            [&](auto t) {
+    return launch_fused_fwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }
 
-extern "C" void stmgcn_cheb_fused_bwd_step(void* stream_v, int dtype,
-                                           const ChebBwdArgs& a) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
-    launch_fused_bwd<decltype(t)>((hipStream_t)stream_v, a);
+extern "C" const char* stmgcn_cheb_fused_bwd_step(void* stream_v, int dtype,
+                                                  const ChebBwdArgs& a) {
+  return stm_dispatch_dtype("stmgcn_cheb_fused_bwd_step: unsupported dtype code", dtype,
+                            [&](auto t) {
+    return launch_fused_bwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }

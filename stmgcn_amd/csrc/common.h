@@ -28,31 +28,40 @@ template <> __device__ __forceinline__ __hip_bfloat16 fromF<__hip_bfloat16>(floa
 template <> __device__ __forceinline__ __half fromF<__half>(float v) { return __float2half(v); }
 
 // ---------------------------------------------------------------------------
+// Launcher status (kernels.h): null, or a static message. stm_launched() is
+// taken directly after each hipLaunchKernelGGL; hipGetLastError neither
+// synchronises nor queries the stream, so it is safe under stream capture.
+inline const char* stm_status(hipError_t e) {
+  return e == hipSuccess ? nullptr : hipGetErrorString(e);
+}
+inline const char* stm_launched() { return stm_status(hipGetLastError()); }
+
 // Host-side dtype dispatch: f(T{}) for the element type of a StmDtype code, so
 // a launcher writes each launch once inside a generic lambda
-// ([&](auto t) { using T = decltype(t); ... }). A code outside the enum
-// launches nothing (bindings.cpp admits only these three).
-template <typename F> void stm_dispatch_dtype(int dtype, F&& f) {
+// ([&](auto t) { using T = decltype(t); ... return stm_launched(); }). f's
+// status is returned; a code outside the enum launches nothing and returns
+// `bad`, the entry point's message for it.
+template <typename F> const char* stm_dispatch_dtype(const char* bad, int dtype, F&& f) {
   switch (dtype) {
-    case STM_F32: f(float{}); break;
-    case STM_BF16: f(__hip_bfloat16{}); break;
-    case STM_F16: f(__half{}); break;
+    case STM_F32: return f(float{});
+    case STM_BF16: return f(__hip_bfloat16{});
+    case STM_F16: return f(__half{});
+    default: return bad;
   }
 }
 // The same for kernels that have no fp32 form (MFMA fragments, packed 16 B
-// moves): any other code is reported under the entry point's name `who`.
-template <typename F> void stm_dispatch_lowp(const char* who, int dtype, F&& f) {
+// moves).
+template <typename F> const char* stm_dispatch_lowp(const char* bad, int dtype, F&& f) {
   switch (dtype) {
-    case STM_BF16: f(__hip_bfloat16{}); break;
-    case STM_F16: f(__half{}); break;
-    default: printf("%s: unsupported dtype %d (bf16/f16 only)\n", who, dtype);
+    case STM_BF16: return f(__hip_bfloat16{});
+    case STM_F16: return f(__half{});
+    default: return bad;
   }
 }
 // A runtime flag as a template argument: f(std::true_type{}) or
 // f(std::false_type{}); the kernel takes decltype(flag)::value.
-template <typename F> void stm_dispatch_bool(bool flag, F&& f) {
-  if (flag) f(std::true_type{});
-  else f(std::false_type{});
+template <typename F> const char* stm_dispatch_bool(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // ---------------------------------------------------------------------------
@@ -208,11 +217,3 @@ __device__ __forceinline__ void stm_store4(T* dst, float a, float b, float c,
   pk.t[2] = fromF<T>(c); pk.t[3] = fromF<T>(d);
   *(uint2*)dst = pk.u;
 }
-
-#define STM_CHECK_HIP(expr)                                                    \
-  do {                                                                          \
-    hipError_t _e = (expr);                                                     \
-    if (_e != hipSuccess) {                                                     \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); \
-    }                                                                           \
-  } while (0)

@@ -262,8 +262,8 @@ dual_fused_bwd_kernel(const StmCsr gft, const StmCsr gbt,
 // MFMA epilogue when gc_fwd_mfma serves the widths, scalar epilogue
 // otherwise. LDS slots: pf tile, pb tile (+ the x tile at k = 1).
 template <typename T>
-void launch_dual_fwd(hipStream_t st, const DualFwdArgs& a) {
-  gc_dispatch_mf<T>(gc_fwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
+const char* launch_dual_fwd(hipStream_t st, const DualFwdArgs& a) {
+  return gc_dispatch_mf<T>(gc_fwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
     constexpr bool MF = decltype(mf)::value;
     hipLaunchKernelGGL((dual_fused_fwd_kernel<T, MF>), gc_grid(a.N, a.B), dim3(256),
                        (a.x0 ? 3 : 2) * gc_slot_bytes(MF), st, a.gf, a.gb,
@@ -274,14 +274,15 @@ void launch_dual_fwd(hipStream_t st, const DualFwdArgs& a) {
                        a.beta, a.first, a.act,
                        (int)gc_vec8(a.N, a.C, {a.xf, a.pf1, a.xb, a.pb1, a.x0, a.pfout,
                                           a.pbout}));
+    return stm_launched();
   });
 }
 
 // MFMA U GEMMs when gc_bwd_mfma serves the widths, scalar loop otherwise.
 // LDS: dz slot + two fp32 U tiles.
 template <typename T>
-void launch_dual_bwd(hipStream_t st, const DualBwdArgs& a) {
-  gc_dispatch_mf<T>(gc_bwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
+const char* launch_dual_bwd(hipStream_t st, const DualBwdArgs& a) {
+  return gc_dispatch_mf<T>(gc_bwd_mfma<T>(a.C, a.Cout), [&](auto mf) {
     constexpr bool MF = decltype(mf)::value;
     hipLaunchKernelGGL((dual_fused_bwd_kernel<T, MF>), gc_grid(a.N, a.B), dim3(256),
                        gc_slot_bytes(MF) + 2 * GC_F32_TILE_BYTES, st, a.gft, a.gbt,
@@ -291,27 +292,26 @@ void launch_dual_bwd(hipStream_t st, const DualBwdArgs& a) {
                        a.beta, a.final_step,
                        (int)gc_vec8(a.N, a.C, {a.xf, a.pf1, a.xb, a.pb1, a.outf, a.outb}),
                        (int)gc_vec8(a.N, a.Cout, {a.dz}));
+    return stm_launched();
   });
 }
 
 }  // namespace
 
-// Host contract (checked in bindings.cpp): bf16/f16 only — no fp32 kernels
-// are instantiated — and C <= 64, Cout <= 64.
-extern "C" void stmgcn_dual_fused_fwd_step(void* stream_v, int dtype,
-                                           const DualFwdArgs& a) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
-    using T = decltype(t);
-    if constexpr (!std::is_same<T, float>::value)
-      launch_dual_fwd<T>((hipStream_t)stream_v, a);
+// bf16/f16 only (no fp32 kernels are instantiated); C <= 64, Cout <= 64 is
+// checked in bindings.cpp.
+extern "C" const char* stmgcn_dual_fused_fwd_step(void* stream_v, int dtype,
+                                                  const DualFwdArgs& a) {
+  return stm_dispatch_lowp("stmgcn_dual_fused_fwd_step: dtype code is not bf16/f16",
+                           dtype, [&](auto t) {
+    return launch_dual_fwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }
 
-extern "C" void stmgcn_dual_fused_bwd_step(void* stream_v, int dtype,
-                                           const DualBwdArgs& a) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
-    using T = decltype(t);
-    if constexpr (!std::is_same<T, float>::value)
-      launch_dual_bwd<T>((hipStream_t)stream_v, a);
+extern "C" const char* stmgcn_dual_fused_bwd_step(void* stream_v, int dtype,
+                                                  const DualBwdArgs& a) {
+  return stm_dispatch_lowp("stmgcn_dual_fused_bwd_step: dtype code is not bf16/f16",
+                           dtype, [&](auto t) {
+    return launch_dual_bwd<decltype(t)>((hipStream_t)stream_v, a);
   });
 }

@@ -33,18 +33,10 @@
 
 #include "common.h"
 
-// SEQ_TILE (= 32) lives in kernels.h; common.h fixes the dA tile layout on it.
-#define RNN_H 64
+// SEQ_TILE (= 32), RNN_H (= 64), MAX_LAYERS and RnnPtrs live in kernels.h;
+// common.h fixes the dA tile layout on SEQ_TILE.
 static_assert(4 * RNN_H == STM_DA_GATES, "dA tile layout assumes 4H = 256");
-#define MAX_LAYERS 8
 #define MAX_T 16
-
-struct RnnPtrs {
-  const void* w_ih[MAX_LAYERS];   // (G*H, C_l) row-major, model dtype
-  const void* w_hh[MAX_LAYERS];   // (G*H, H)
-  const void* b_ih[MAX_LAYERS];   // (G*H,) model dtype
-  const void* b_hh[MAX_LAYERS];   // (G*H,) model dtype
-};
 
 // (The MFMA fragment types, mfma16x16x32 and the LDS swizzle lds_swz for
 // 128 B tile rows live in common.h — shared with the wgrad and gconv kernels.)
@@ -422,52 +414,45 @@ lstm_fwd_kernel(const T* __restrict__ x,    // (S, Tst, C_in)
   }
 }
 
-// Per-layer pointer tables of one launch; the backward passes no biases.
-static RnnPtrs rnn_ptrs(int L, const void** w_ih, const void** w_hh,
-                        const void** b_ih, const void** b_hh) {
-  RnnPtrs p{};
-  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
-    p.w_ih[l] = w_ih[l]; p.w_hh[l] = w_hh[l];
-    p.b_ih[l] = b_ih ? b_ih[l] : nullptr;
-    p.b_hh[l] = b_hh ? b_hh[l] : nullptr;
-  }
-  return p;
-}
-
 // f(CIN1, GRU) as std::bool_constant values: the kernel variant of a launch
-template <typename F> void rnn_dispatch_variant(int cin, int gru, F&& f) {
-  stm_dispatch_bool(cin == 1, [&](auto cin1) {
-    stm_dispatch_bool(gru != 0, [&](auto is_gru) { f(cin1, is_gru); });
+template <typename F> const char* rnn_dispatch_variant(int cin, int gru, F&& f) {
+  return stm_dispatch_bool(cin == 1, [&](auto cin1) {
+    return stm_dispatch_bool(gru != 0, [&](auto is_gru) { return f(cin1, is_gru); });
   });
 }
 
-extern "C" void stmgcn_lstm_fwd(void* stream, int dtype, const void* x,
-                                void* out, void* hseq_g, void* cseq_g,
-                                void* gates_g, const void** w_ih,
-                                const void** w_hh, const void** b_ih,
-                                const void** b_hh, int S, int Tst, int L,
-                                int cin, int ret_seq, int gru) {
-  const RnnPtrs p = rnn_ptrs(L, w_ih, w_hh, b_ih, b_hh);
-  const int nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
-  stm_dispatch_lowp("stmgcn_lstm_fwd", dtype, [&](auto t) {
+// the shapes both RNN kernels serve
+static bool rnn_serves(int S, int Tst, int L, int cin) {
+  return S >= 1 && L >= 1 && L <= MAX_LAYERS && Tst >= 1 && Tst <= MAX_T &&
+         (cin == 1 || cin == RNN_H);
+}
+
+extern "C" const char* stmgcn_lstm_fwd(void* stream, int dtype, const LstmFwdArgs& a) {
+  if (!rnn_serves(a.S, a.Tst, a.L, a.cin))
+    return "stmgcn_lstm_fwd: serves 1..8 layers, 1..16 steps, input width 1 or 64";
+  const int nblk = (a.S + SEQ_TILE - 1) / SEQ_TILE;
+  return stm_dispatch_lowp("stmgcn_lstm_fwd: dtype code is not bf16/f16", dtype, [&](auto t) {
     using T = decltype(t);
     // two h slots + the CIN1 scalar input stage
     const size_t lds_bytes =
-        2 * SEQ_TILE * 128 + (cin == 1 ? Tst * SEQ_TILE * sizeof(T) : 0);
-    rnn_dispatch_variant(cin, gru, [&](auto cin1, auto is_gru) {
+        2 * SEQ_TILE * 128 + (a.cin == 1 ? a.Tst * SEQ_TILE * sizeof(T) : 0);
+    return rnn_dispatch_variant(a.cin, a.gru, [&](auto cin1, auto is_gru) {
       hipLaunchKernelGGL(
           (lstm_fwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>),
-          dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)x,
-          (T*)out, (T*)hseq_g, (T*)cseq_g, (T*)gates_g, p, S, Tst, L, ret_seq);
+          dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)a.x,
+          (T*)a.out, (T*)a.hseq, (T*)a.cseq, (T*)a.gates, a.w, a.S, a.Tst, a.L,
+          a.ret_seq);
+      return stm_launched();
     });
   });
 }
 
-extern "C" void stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
-                                  void* D) {
+extern "C" const char* stmgcn_mfma_probe(void* stream_v, const void* A, const void* B,
+                                         void* D) {
   hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0,
                      (hipStream_t)stream_v, (const __hip_bfloat16*)A,
                      (const __hip_bfloat16*)B, (float*)D);
+  return stm_launched();
 }
 
 // ===========================================================================
@@ -1091,31 +1076,29 @@ lstm_bwd_kernel(const T* __restrict__ dout,     // (S,H) or (S,Tst,H)
   }
 }
 
-extern "C" void stmgcn_lstm_bwd(void* stream, int dtype, const void* dout,
-                                const void* x, const void* cseq_g,
-                                const void* gates_g, const void** w_ihT,
-                                const void** w_hhT, void* dx, void* dA_g,
-                                void* dh_g, int S, int Tst, int L, int cin,
-                                int ret_seq, int gru) {
-  const RnnPtrs p = rnn_ptrs(L, w_ihT, w_hhT, nullptr, nullptr);
-  const int nblk = (S + SEQ_TILE - 1) / SEQ_TILE;
+extern "C" const char* stmgcn_lstm_bwd(void* stream, int dtype, const LstmBwdArgs& a) {
+  if (!rnn_serves(a.S, a.Tst, a.L, a.cin))
+    return "stmgcn_lstm_bwd: serves 1..8 layers, 1..16 steps, input width 1 or 64";
+  const int nblk = (a.S + SEQ_TILE - 1) / SEQ_TILE;
   // the dA tile + the CIN1 dx reduction scratch + the lane-private parking of
   // the saves (gates 32 B per m-tile, dh and two cell parities 8 B each) +
   // W_hh^T of one layer: 76.5 KB, above the 64 KB a launch gets unasked
   const size_t lds_bytes = SEQ_TILE * 512 + 4 * SEQ_TILE * sizeof(float)
                            + 256 * (SEQ_TILE / 16) * (32 + 3 * 8)
                            + RNN_H * 4 * RNN_H * 2;
-  stm_dispatch_lowp("stmgcn_lstm_bwd", dtype, [&](auto t) {
+  return stm_dispatch_lowp("stmgcn_lstm_bwd: dtype code is not bf16/f16", dtype, [&](auto t) {
     using T = decltype(t);
-    rnn_dispatch_variant(cin, gru, [&](auto cin1, auto is_gru) {
-      STM_CHECK_HIP(hipFuncSetAttribute(
-          (const void*)lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>,
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-      hipLaunchKernelGGL(
-          (lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>),
-          dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream, (const T*)dout,
-          (const T*)x, (const T*)cseq_g, (const T*)gates_g, p, (T*)dx,
-          (T*)dA_g, (T*)dh_g, S, Tst, L, ret_seq);
+    return rnn_dispatch_variant(a.cin, a.gru, [&](auto cin1, auto is_gru) {
+      auto* kernel = lstm_bwd_kernel<T, decltype(cin1)::value, decltype(is_gru)::value>;
+      if (const char* e = stm_status(hipFuncSetAttribute(
+              (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+              (int)lds_bytes)))
+        return e;
+      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), lds_bytes, (hipStream_t)stream,
+                         (const T*)a.dout, (const T*)a.x, (const T*)a.cseq,
+                         (const T*)a.gates, a.w, (T*)a.dx, (T*)a.dA, (T*)a.dh, a.S,
+                         a.Tst, a.L, a.ret_seq);
+      return stm_launched();
     });
   });
 }
@@ -1149,23 +1132,17 @@ lstm_pack_bwd_weights_kernel(PackMats pm, unsigned short* __restrict__ dst) {
     out[(long)c * 256 + r0 + lo] = tile[lo][c];
 }
 
-extern "C" void stmgcn_lstm_pack_bwd_weights(void* stream, const void** w_ih,
-                                             const void** w_hh, int L, int cin,
-                                             void* dst) {
+extern "C" const char* stmgcn_lstm_pack_bwd_weights(void* stream, const void** w_ih,
+                                                    const void** w_hh, int L,
+                                                    int cin, void* dst) {
+  if (L < 1 || L > MAX_LAYERS) return "stmgcn_lstm_pack_bwd_weights: layer count outside 1..8";
   PackMats pm{};
-  long off = 0;
-  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {   // all W_ih^T, then all W_hh^T
-    pm.src[l] = (const unsigned short*)w_ih[l];
-    pm.cols[l] = l == 0 ? cin : 64;
-    pm.dst_off[l] = off;
-    off += 256L * pm.cols[l];
-  }
-  for (int l = 0; l < L && l < MAX_LAYERS; ++l) {
-    pm.src[L + l] = (const unsigned short*)w_hh[l];
-    pm.cols[L + l] = 64;
-    pm.dst_off[L + l] = off;
-    off += 256L * 64;
+  for (int i = 0; i < 2 * L; ++i) {   // all W_ih^T, then all W_hh^T
+    pm.src[i] = (const unsigned short*)(i < L ? w_ih[i] : w_hh[i - L]);
+    pm.cols[i] = i < L ? lstm_packT_cols(i, cin) : RNN_H;
+    pm.dst_off[i] = lstm_packT_off(i, cin);
   }
   hipLaunchKernelGGL(lstm_pack_bwd_weights_kernel, dim3(4, 2 * L), dim3(256), 0,
                      (hipStream_t)stream, pm, (unsigned short*)dst);
+  return stm_launched();
 }

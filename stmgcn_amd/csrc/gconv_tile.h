@@ -63,11 +63,11 @@ inline bool gc_vec8(int N, int C, std::initializer_list<const void*> ptrs) {
 
 // f(std::true_type) when the MFMA variant serves, f(std::false_type) otherwise;
 // fp32 never instantiates the MFMA variant.
-template <typename T, typename F> void gc_dispatch_mf(bool mf, F&& f) {
+template <typename T, typename F> const char* gc_dispatch_mf(bool mf, F&& f) {
   if constexpr (!std::is_same<T, float>::value) {
-    if (mf) { f(std::true_type{}); return; }
+    if (mf) return f(std::true_type{});
   }
-  f(std::false_type{});
+  return f(std::false_type{});
 }
 
 // ---- device side ----------------------------------------------------------

@@ -730,11 +730,12 @@ __global__ void masked_loss_bwd_kernel(const T* __restrict__ diff,
 }
 
 // f(std::integral_constant<int, kind>{}) for kind 0 (mse), 1 (mae), 2 (huber)
-template <typename F> void mloss_dispatch_kind(int kind, F&& f) {
+template <typename F> const char* mloss_dispatch_kind(int kind, F&& f) {
   switch (kind) {
-    case 0: f(std::integral_constant<int, 0>{}); break;
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return "stmgcn_masked_loss: kind is not 0 (mse), 1 (mae) or 2 (huber)";
   }
 }
 
@@ -816,275 +817,297 @@ inline dim3 grid1d(long total) { return dim3((unsigned)((total + 255) / 256)); }
 // ---- entry points: T comes from the dtype code (stm_dispatch_dtype) --------
 extern "C" {
 
-void stmgcn_seqsum_permute(void* stream, int dtype, const void* obs, void* out,
-                           int B, int Tst, int N, int C) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_seqsum_permute(void* stream, int dtype, const void* obs, void* out,
+                                  int B, int Tst, int N, int C) {
+  return stm_dispatch_dtype("stmgcn_seqsum_permute: unsupported dtype code", dtype,
+                            [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(seqsum_permute_kernel<T>, grid1d((long)B * N * Tst),
                        dim3(256), 0, (hipStream_t)stream, (const T*)obs, (T*)out,
                        B, Tst, N, C);
+    return stm_launched();
   });
 }
 
-void stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs,
-                               void* dobs, int B, int Tst, int N, int C) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_seqsum_permute_bwd(void* stream, int dtype, const void* dxs,
+                                      void* dobs, int B, int Tst, int N, int C) {
+  return stm_dispatch_dtype("stmgcn_seqsum_permute_bwd: unsupported dtype code", dtype,
+                            [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(seqsum_permute_bwd_kernel<T>,
                        grid1d((long)B * Tst * N * C), dim3(256), 0,
                        (hipStream_t)stream, (const T*)dxs, (T*)dobs, B, Tst, N, C);
+    return stm_launched();
   });
 }
 
-// z (B*T floats) and tickets (B words) share one zero-filled allocation (z
-// doubles as the zsum atomic target); node_major: out is (B,N,T,C) instead of
-// (B,T,N,C)
-void stmgcn_gate_fwd(void* stream, int dtype, const void* g, const void* xs,
-                     const void* fcw, const void* fcb, const void* obs,
-                     float* z, float* u, float* s, unsigned* tickets, void* out,
-                     int B, int Tst, int N, int C, int node_major) {
+// z doubles as the zsum atomic target (layout: gate_ws, kernels.h)
+const char* stmgcn_gate_fwd(void* stream, int dtype, const GateFwdArgs& a) {
   hipStream_t st = (hipStream_t)stream;
+  const int B = a.B, Tst = a.Tst, N = a.N, C = a.C;
   const long total = (long)B * Tst * N * C;
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  const GateWs ws = gate_ws(B, Tst, false);
+  float* z = a.ws + ws.z;
+  unsigned* tickets = (unsigned*)(a.ws + ws.tickets);
+  return stm_dispatch_dtype("stmgcn_gate_fwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(gate_fwd_reduce_kernel<T>, dim3(gate_chunks(B, N), B),
-                       dim3(256), 0, st, (const T*)g, (const T*)xs, z,
-                       (const T*)fcw, (const T*)fcb, u, s, tickets, N, Tst);
-    stm_dispatch_bool(node_major != 0, [&](auto nm) {
+                       dim3(256), 0, st, (const T*)a.g, (const T*)a.xs, z,
+                       (const T*)a.fcw, (const T*)a.fcb, a.u, a.s, tickets, N, Tst);
+    if (const char* e = stm_launched()) return e;
+    return stm_dispatch_bool(a.node_major != 0, [&](auto nm) {
       hipLaunchKernelGGL((gate_scale_kernel<T, decltype(nm)::value>),
-                         grid1d(total), dim3(256), 0, st, (const T*)obs, s,
-                         (T*)out, Tst, N, C, total);
+                         grid1d(total), dim3(256), 0, st, (const T*)a.obs, a.s,
+                         (T*)a.out, Tst, N, C, total);
+      return stm_launched();
     });
   });
 }
 
-// dz (B*T floats) and tickets (B + 1 words) share one zero-filled allocation
-// (dz doubles as the ds atomic target); dw_f/db_f: fp32 sums over the batch,
-// dw/db the same in `dtype`; dobs may be null (obs needs no gradient);
-// node_major: dout is (B,N,T,C)
-void stmgcn_gate_bwd(void* stream, int dtype, const void* dout, const void* obs,
-                     const void* fcw, const float* z, const float* u,
-                     const float* s, float* dz, float* dw_part, float* db_part,
-                     unsigned* tickets, float* dw_f, float* db_f, void* dw,
-                     void* db, void* dobs, void* dg, int B, int Tst, int N, int C,
-                     int node_major) {
+// dz doubles as the ds atomic target (layout: gate_ws, kernels.h)
+const char* stmgcn_gate_bwd(void* stream, int dtype, const GateBwdArgs& a) {
   hipStream_t st = (hipStream_t)stream;
+  const int B = a.B, Tst = a.Tst, N = a.N, C = a.C;
   const long total = (long)B * Tst * N * C;
   const float invN = 1.f / (float)N;
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  const GateWs ws = gate_ws(B, Tst, true);
+  float* dz = a.ws + ws.z;
+  unsigned* tickets = (unsigned*)(a.ws + ws.tickets);
+  return stm_dispatch_dtype("stmgcn_gate_bwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
-    stm_dispatch_bool(node_major != 0, [&](auto nm) {
+    return stm_dispatch_bool(a.node_major != 0, [&](auto nm) {
       constexpr bool NM = decltype(nm)::value;
       hipLaunchKernelGGL((gate_bwd_reduce_kernel<T, NM>),
                          dim3(gate_chunks(B, (long)N * C), B), dim3(256), 0, st,
-                         (const T*)dout, (const T*)obs, dz, (const T*)fcw, z, u,
-                         s, dw_part, db_part, tickets, dw_f, db_f, (T*)dw,
-                         (T*)db, N, C, Tst);
+                         (const T*)a.dout, (const T*)a.obs, dz, (const T*)a.fcw, a.z,
+                         a.u, a.s, a.dw_part, a.db_part, tickets, a.dw_f, a.db_f,
+                         (T*)a.dw, (T*)a.db, N, C, Tst);
+      if (const char* e = stm_launched()) return e;
       hipLaunchKernelGGL((gate_bwd_scatter_kernel<T, NM>), grid1d(total),
-                         dim3(256), 0, st, (const T*)dout, s, dz, (T*)dobs,
-                         (T*)dg, Tst, N, C, invN, total);
+                         dim3(256), 0, st, (const T*)a.dout, a.s, dz, (T*)a.dobs,
+                         (T*)a.dg, Tst, N, C, invN, total);
+      return stm_launched();
     });
   });
 }
 
-void stmgcn_head_fwd(void* stream, int dtype, const void* f0, const void* f1,
-                     const void* f2, const void* w, const void* bias, void* y,
-                     void* fsum, int G, long BN) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_head_fwd(void* stream, int dtype, const void* f0, const void* f1,
+                            const void* f2, const void* w, const void* bias, void* y,
+                            void* fsum, int G, long BN) {
+  return stm_dispatch_dtype("stmgcn_head_fwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(head_fwd_kernel<T>, grid1d(BN * 64), dim3(256), 0,
                        (hipStream_t)stream, (const T*)f0, (const T*)f1,
                        (const T*)f2, (const T*)w, (const T*)bias, (T*)y,
                        (T*)fsum, G, BN);
+    return stm_launched();
   });
 }
 
-void stmgcn_head_bwd(void* stream, int dtype, const void* dy, const void* w,
-                     void* dfeat, int G, long BN) {
+const char* stmgcn_head_bwd(void* stream, int dtype, const void* dy, const void* w,
+                            void* dfeat, int G, long BN) {
   const long total = BN * G;
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  return stm_dispatch_dtype("stmgcn_head_bwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(head_bwd_kernel<T>, grid1d(total), dim3(256), 0,
                        (hipStream_t)stream, (const T*)dy, (const T*)w,
                        (T*)dfeat, G, total);
+    return stm_launched();
   });
 }
 
-// ticket == null: the accumulate-only form (fp32 sums left in dw / db);
-// otherwise the finishing form, dw_out (G,) / db_out (1,) in the dtype of dy
-static void head_wgrad_launch(void* stream, int dtype, const void* dy,
-                              const void* fsum, float* dw, float* db,
-                              unsigned* ticket, void* dw_out, void* db_out,
-                              int G, long BN) {
-  long nblk = (BN + 255) / 256;   // fill the chip: 128+ blocks at bench size
+// fill the chip: 128+ blocks at bench size
+static long head_wgrad_blocks(long BN) {
+  long nblk = (BN + 255) / 256;
   if (nblk > 512) nblk = 512;
-  if (nblk < 1) nblk = 1;
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  return nblk < 1 ? 1 : nblk;
+}
+
+// a.dw_out == null: the accumulate-only form (fp32 sums left in a.ws)
+const char* stmgcn_head_wgrad(void* stream, int dtype, const HeadWgradArgs& a) {
+  if (a.O != 1 || a.G < 1 || a.G > 64) return "stmgcn_head_wgrad: serves O == 1, G <= 64";
+  const HeadWgradWs ws = head_wgrad_ws(a.G, 1);
+  const bool finishing = a.dw_out != nullptr;
+  unsigned* ticket = finishing ? (unsigned*)(a.ws + ws.ticket) : nullptr;
+  return stm_dispatch_dtype("stmgcn_head_wgrad: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
-    stm_dispatch_bool(ticket != nullptr, [&](auto fin) {
+    return stm_dispatch_bool(finishing, [&](auto fin) {
       hipLaunchKernelGGL((head_wgrad_kernel<T, decltype(fin)::value>),
-                         dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                         (const T*)dy, (const T*)fsum, dw, db, G, BN, ticket,
-                         (T*)dw_out, (T*)db_out);
+                         dim3((unsigned)head_wgrad_blocks(a.BN)), dim3(256), 0,
+                         (hipStream_t)stream, (const T*)a.dy, (const T*)a.fsum,
+                         a.ws + ws.dw, a.ws + ws.db, a.G, a.BN, ticket, (T*)a.dw_out,
+                         (T*)a.db_out);
+      return stm_launched();
     });
   });
 }
 
-void stmgcn_head_wgrad(void* stream, int dtype, const void* dy,
-                       const void* fsum, float* dw, float* db, int G,
-                       long BN) {
-  head_wgrad_launch(stream, dtype, dy, fsum, dw, db, nullptr, nullptr, nullptr,
-                    G, BN);
+static bool head_multi_serves(int G, int O) {
+  return O >= 2 && O <= 32 && G >= 8 && G <= 64 && G % 8 == 0;
 }
 
-void stmgcn_head_wgrad_grads(void* stream, int dtype, const void* dy,
-                             const void* fsum, float* dw, float* db,
-                             unsigned* ticket, void* dw_out, void* db_out,
-                             int G, long BN) {
-  head_wgrad_launch(stream, dtype, dy, fsum, dw, db, ticket, dw_out, db_out, G,
-                    BN);
-}
-
-// wide head, 2 <= O <= 32, G <= 64 with G % 8 == 0 (bindings.cpp checks): one
-// wave per 16 rows, 64 rows per workgroup
-void stmgcn_head_multi_fwd(void* stream, int dtype, const void* f0,
-                           const void* f1, const void* f2, const void* w,
-                           const void* bias, void* y, void* fsum, int G, int O,
-                           long BN) {
-  if (BN <= 0) return;
+// wide head: one wave per 16 rows, 64 rows per workgroup
+const char* stmgcn_head_multi_fwd(void* stream, int dtype, const void* f0,
+                                  const void* f1, const void* f2, const void* w,
+                                  const void* bias, void* y, void* fsum, int G, int O,
+                                  long BN) {
+  if (!head_multi_serves(G, O))
+    return "stmgcn_head_multi_fwd: serves 2 <= O <= 32, G <= 64 with G % 8 == 0";
+  if (BN <= 0) return nullptr;
   const dim3 grid((unsigned)((BN + 63) / 64));
-  stm_dispatch_lowp("stmgcn_head_multi_fwd", dtype, [&](auto t) {
+  return stm_dispatch_lowp("stmgcn_head_multi_fwd: dtype code is not bf16/f16", dtype,
+                           [&](auto t) {
     using T = decltype(t);
-    stm_dispatch_bool(O > 16, [&](auto two) {
+    return stm_dispatch_bool(O > 16, [&](auto two) {
       constexpr int NCT = decltype(two)::value ? 2 : 1;
       hipLaunchKernelGGL((head_multi_fwd_kernel<T, NCT>), grid, dim3(256), 0,
                          (hipStream_t)stream, (const T*)f0, (const T*)f1,
                          (const T*)f2, (const T*)w, (const T*)bias, (T*)y,
                          (T*)fsum, G, O, BN);
+      return stm_launched();
     });
   });
 }
 
-void stmgcn_head_multi_bwd(void* stream, int dtype, const void* dy,
-                           const void* w, void* dfeat, int G, int O, long BN) {
-  if (BN <= 0) return;
-  stm_dispatch_lowp("stmgcn_head_multi_bwd", dtype, [&](auto t) {
+const char* stmgcn_head_multi_bwd(void* stream, int dtype, const void* dy,
+                                  const void* w, void* dfeat, int G, int O, long BN) {
+  if (!head_multi_serves(G, O))
+    return "stmgcn_head_multi_bwd: serves 2 <= O <= 32, G <= 64 with G % 8 == 0";
+  if (BN <= 0) return nullptr;
+  return stm_dispatch_lowp("stmgcn_head_multi_bwd: dtype code is not bf16/f16", dtype,
+                           [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(head_multi_bwd_kernel<T>,
                        dim3((unsigned)((BN + 63) / 64)), dim3(256), 0,
                        (hipStream_t)stream, (const T*)dy, (const T*)w,
                        (T*)dfeat, G, O, BN);
+    return stm_launched();
   });
 }
 
-// ticket == null: the accumulate-only form (fp32 sums left in dw (O*G) / db
-// (O)); otherwise the finishing form, dw_out (O, G) / db_out (O,) in `dtype`
-void stmgcn_head_multi_wgrad(void* stream, int dtype, const void* dy,
-                             const void* fsum, float* dw, float* db,
-                             unsigned* ticket, void* dw_out, void* db_out,
-                             int G, int O, long BN) {
-  long nblk = (BN + 255) / 256;   // as head_wgrad: 128 blocks at bench size
-  if (nblk > 512) nblk = 512;
-  if (nblk < 1) nblk = 1;
-  stm_dispatch_lowp("stmgcn_head_multi_wgrad", dtype, [&](auto t) {
+// a.dw_out == null: the accumulate-only form (fp32 sums left in a.ws)
+const char* stmgcn_head_multi_wgrad(void* stream, int dtype, const HeadWgradArgs& a) {
+  if (!head_multi_serves(a.G, a.O))
+    return "stmgcn_head_multi_wgrad: serves 2 <= O <= 32, G <= 64 with G % 8 == 0";
+  const HeadWgradWs ws = head_wgrad_ws(a.G, a.O);
+  const bool finishing = a.dw_out != nullptr;
+  unsigned* ticket = finishing ? (unsigned*)(a.ws + ws.ticket) : nullptr;
+  return stm_dispatch_lowp("stmgcn_head_multi_wgrad: dtype code is not bf16/f16", dtype,
+                           [&](auto t) {
     using T = decltype(t);
-    stm_dispatch_bool(ticket != nullptr, [&](auto fin) {
+    return stm_dispatch_bool(finishing, [&](auto fin) {
       hipLaunchKernelGGL((head_multi_wgrad_kernel<T, decltype(fin)::value>),
-                         dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                         (const T*)dy, (const T*)fsum, dw, db, G, O, BN, ticket,
-                         (T*)dw_out, (T*)db_out);
+                         dim3((unsigned)head_wgrad_blocks(a.BN)), dim3(256), 0,
+                         (hipStream_t)stream, (const T*)a.dy, (const T*)a.fsum,
+                         a.ws + ws.dw, a.ws + ws.db, a.G, a.O, a.BN, ticket,
+                         (T*)a.dw_out, (T*)a.db_out);
+      return stm_launched();
     });
   });
 }
 
-// ws: 3 zero-filled words (fp32 sum, unsigned count, ticket); res: loss and
-// 1 / max(count, 1); kind 0 mse, 1 mae, 2 huber
-void stmgcn_masked_loss_fwd(void* stream, int dtype, int kind, const void* pred,
-                            const void* tgt, float* ws, float* res, void* diff,
-                            long n) {
+// ws: the MLOSS_WS_* words of kernels.h (fp32 sum, unsigned count, ticket);
+// res: loss and 1 / max(count, 1); kind 0 mse, 1 mae, 2 huber
+const char* stmgcn_masked_loss_fwd(void* stream, int dtype, int kind, const void* pred,
+                                   const void* tgt, float* ws, float* res, void* diff,
+                                   long n) {
   const dim3 grid((unsigned)((n + MLOSS_PER_BLOCK - 1) / MLOSS_PER_BLOCK));
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  return stm_dispatch_dtype("stmgcn_masked_loss_fwd: unsupported dtype code", dtype,
+                            [&](auto t) {
     using T = decltype(t);
-    mloss_dispatch_kind(kind, [&](auto k) {
+    return mloss_dispatch_kind(kind, [&](auto k) {
       hipLaunchKernelGGL((masked_loss_fwd_kernel<T, decltype(k)::value>), grid,
                          dim3(256), 0, (hipStream_t)stream, (const T*)pred,
-                         (const T*)tgt, ws, (unsigned*)(ws + 1),
-                         (unsigned*)(ws + 2), res, (T*)diff, n);
+                         (const T*)tgt, ws + MLOSS_WS_SUM,
+                         (unsigned*)(ws + MLOSS_WS_COUNT),
+                         (unsigned*)(ws + MLOSS_WS_TICKET), res, (T*)diff, n);
+      return stm_launched();
     });
   });
 }
 
-void stmgcn_masked_loss_bwd(void* stream, int dtype, int kind, const void* diff,
-                            const float* res, const float* gscale, void* dpred,
-                            long n) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_masked_loss_bwd(void* stream, int dtype, int kind, const void* diff,
+                                   const float* res, const float* gscale, void* dpred,
+                                   long n) {
+  return stm_dispatch_dtype("stmgcn_masked_loss_bwd: unsupported dtype code", dtype,
+                            [&](auto t) {
     using T = decltype(t);
-    mloss_dispatch_kind(kind, [&](auto k) {
+    return mloss_dispatch_kind(kind, [&](auto k) {
       hipLaunchKernelGGL((masked_loss_bwd_kernel<T, decltype(k)::value>),
                          grid1d(n), dim3(256), 0, (hipStream_t)stream,
                          (const T*)diff, res, gscale, (T*)dpred, n);
+      return stm_launched();
     });
   });
 }
 
-void stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,
-                     void* dz, long n) {
-  if (n <= 0) return;
+const char* stmgcn_relu_bwd(void* stream, int dtype, const void* dy, const void* y,
+                            void* dz, long n) {
+  if (n <= 0) return nullptr;
   const int vec = (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dz) & 15) == 0;
-  stm_dispatch_lowp("stmgcn_relu_bwd", dtype, [&](auto t) {
+  return stm_dispatch_lowp("stmgcn_relu_bwd: dtype code is not bf16/f16", dtype,
+                           [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3((unsigned)((n + 2047) / 2048)),
                        dim3(256), 0, (hipStream_t)stream, (const T*)dy,
                        (const T*)y, (T*)dz, n, vec);
+    return stm_launched();
   });
 }
 
-void stmgcn_mse_fwd(void* stream, int dtype, const void* pred, const void* tgt,
-                    float* loss, void* diff, long n) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_mse_fwd(void* stream, int dtype, const void* pred, const void* tgt,
+                           float* loss, void* diff, long n) {
+  return stm_dispatch_dtype("stmgcn_mse_fwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(mse_fwd_kernel<T>, grid1d(n), dim3(256), 0,
                        (hipStream_t)stream, (const T*)pred, (const T*)tgt, loss,
                        (T*)diff, n);
+    return stm_launched();
   });
 }
 
-void stmgcn_mse_bwd(void* stream, int dtype, const void* diff, const float* gscale,
-                    void* dpred, long n) {
-  stm_dispatch_dtype(dtype, [&](auto t) {
+const char* stmgcn_mse_bwd(void* stream, int dtype, const void* diff,
+                           const float* gscale, void* dpred, long n) {
+  return stm_dispatch_dtype("stmgcn_mse_bwd: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(mse_bwd_kernel<T>, grid1d(n), dim3(256), 0,
                        (hipStream_t)stream, (const T*)diff, gscale, (T*)dpred,
                        2.f / (float)n, n);
+    return stm_launched();
   });
 }
 
-void stmgcn_adam(void* stream, int dtype, float* master, void* param,
-                 const void* grad, float* m, float* v, float* hyper,
-                 long n) {
+const char* stmgcn_adam(void* stream, int dtype, float* master, void* param,
+                        const void* grad, float* m, float* v, float* hyper, long n) {
+  if (dtype < STM_F32 || dtype > STM_F16) return "stmgcn_adam: unsupported dtype code";
   hipLaunchKernelGGL(adam_prep_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper);
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  if (const char* e = stm_launched()) return e;
+  return stm_dispatch_dtype("stmgcn_adam: unsupported dtype code", dtype, [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(adam_kernel<T>, grid1d(n), dim3(256), 0,
                        (hipStream_t)stream, master, (T*)param, (const T*)grad, m,
                        v, hyper, n);
+    return stm_launched();
   });
 }
 
-void stmgcn_gather_grads(void* stream, int dtype, const void** srcs,
-                         const long* ofs, const int* lens, int nseg,
-                         void* arena) {
+const char* stmgcn_gather_grads(void* stream, int dtype, const void** srcs,
+                                const long* ofs, const int* lens, int nseg,
+                                void* arena) {
+  if (nseg < 1 || nseg > 64) return "stmgcn_gather_grads: segment count outside 1..64";
   GatherSeg a;
   int maxlen = 1;
-  for (int i = 0; i < nseg && i < 64; ++i) {
+  for (int i = 0; i < nseg; ++i) {
     a.src[i] = srcs[i]; a.ofs[i] = ofs[i]; a.len[i] = lens[i];
     if (lens[i] > maxlen) maxlen = lens[i];
   }
   const int chunks = min(8, (maxlen + 2047) / 2048);
-  stm_dispatch_dtype(dtype, [&](auto t) {
+  return stm_dispatch_dtype("stmgcn_gather_grads: unsupported dtype code", dtype,
+                            [&](auto t) {
     using T = decltype(t);
     hipLaunchKernelGGL(gather_grads_kernel<T>, dim3(nseg, chunks), dim3(256), 0,
                        (hipStream_t)stream, a, (T*)arena, nseg);
+    return stm_launched();
   });
 }
 

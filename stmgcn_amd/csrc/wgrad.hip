@@ -99,7 +99,7 @@ __device__ __forceinline__ void wgrad_uniform_form(int form, F&& f) {
 // layer's ticket (stm_last_arriver, common.h); the last one of a layer reads
 // that layer's 129 KiB of fp32 sums back and writes dw_ih, dw_hh, db_ih,
 // db_hh in the parameter dtype and in their final shapes into `fin.out`
-// (layout: lstm_grads_layer_off). One ticket per layer, so up to L last
+// (layout: lstm_grads_layer_off, kernels.h). One ticket per layer, so up to L last
 // arrivers share the conversion. GRU rows are un-packed on the way
 // (q-slots [r|z|n_in|n_hid]: dw_ih/db_ih = rows [:3H], dw_hh/db_hh = rows
 // [:2H] + [3H:]); LSTM writes the one bias sum to both db_ih and db_hh.
@@ -109,11 +109,6 @@ struct LstmFin {
   T* out;              // flat parameter-dtype gradient buffer
   int gru, cin;
 };
-
-// element offset of layer l's [dw_ih | dw_hh | db_ih | db_hh] block
-__host__ __device__ inline long lstm_grads_layer_off(int l, int GH, int cin) {
-  return l == 0 ? 0 : (long)GH * (cin + 64 + 2) + (long)(l - 1) * GH * (64 + 64 + 2);
-}
 
 template <typename T, bool FIN>
 __global__ void __launch_bounds__(512, 1)
@@ -406,62 +401,42 @@ lstm_wgrad_kernel(const T* __restrict__ dA, const T* __restrict__ hseq,
   }
 }
 
-// tickets/out == null: the accumulate-only form (fp32 sums left in place)
-static void lstm_wgrad_launch(void* stream, int dtype, const void* dA,
-                              const void* hseq, const void* x, float* dwih,
-                              float* dwhh, float* db, long R, long S_pad,
-                              int S, int Tst, int L, int cin,
-                              unsigned* tickets, void* out, int gru) {
-  if (R <= 0 || R % SEQ_TILE != 0) {
-    printf("stmgcn_lstm_wgrad: R=%ld is not a whole number of dA tiles\n", R);
-    return;
-  }
+// a.out == null: the accumulate-only form (fp32 sums left in a.ws)
+extern "C" const char* stmgcn_lstm_wgrad(void* stream, int dtype, const LstmWgradArgs& a) {
+  const long R = a.R;
+  const int L = a.L;
+  if (L < 1 || L > MAX_LAYERS) return "stmgcn_lstm_wgrad: layer count outside 1..8";
+  if (R <= 0 || R % SEQ_TILE != 0)
+    return "stmgcn_lstm_wgrad: R is not a whole number of dA tiles";
   // Chunks are whole 32-row tiles of the tiled dA stream: at most one per
   // 1024 rows, and at most 256 / L per layer, i.e. one workgroup per CU in a
   // single round. Two rounds of half-length chunks (512 / L) measured slower,
   // alone and in the step (profiles/wgrad_load_pipeline.md): twice the
   // prologues, dead prefetches and atomics for the same stream.
   const long ntile = R / SEQ_TILE;
-  if (ntile >= (1L << 31)) {
-    printf("stmgcn_lstm_wgrad: R=%ld has too many dA tiles\n", R);
-    return;
-  }
-  const long target = 256 / (L > 0 ? L : 1);
+  if (ntile >= (1L << 31)) return "stmgcn_lstm_wgrad: too many dA tiles";
+  const long target = 256 / L;
   long nchunks = (R + 1023) / 1024;
   if (nchunks > target) nchunks = target;
   if (nchunks < 1) nchunks = 1;
   const long tpc = (ntile + nchunks - 1) / nchunks;   // tiles per workgroup
   nchunks = (ntile + tpc - 1) / tpc;
   const size_t lds = 2 * 2 * 8192;   // double-buffered hpT | hxT, 64-row steps
-  stm_dispatch_lowp("stmgcn_lstm_wgrad", dtype, [&](auto t) {
+  const bool finishing = a.out != nullptr;
+  const LstmWgradWs ws = lstm_wgrad_ws(L, finishing);
+  unsigned* tickets = finishing ? (unsigned*)(a.ws + ws.tickets) : nullptr;
+  return stm_dispatch_lowp("stmgcn_lstm_wgrad: dtype code is not bf16/f16", dtype, [&](auto t) {
     using T = decltype(t);
-    const LstmFin<T> fin{tickets, (T*)out, gru, cin};
-    stm_dispatch_bool(out != nullptr, [&](auto finc) {
+    const LstmFin<T> fin{tickets, (T*)a.out, finishing ? a.gru : 0, a.cin};
+    return stm_dispatch_bool(finishing, [&](auto finc) {
       hipLaunchKernelGGL((lstm_wgrad_kernel<T, decltype(finc)::value>),
                          dim3((unsigned)nchunks, L), dim3(512), lds,
-                         (hipStream_t)stream, (const T*)dA, (const T*)hseq,
-                         (const T*)x, dwih, dwhh, db, R, S_pad, S, Tst, L,
-                         cin == 1 ? 1 : 0, tpc, fin);
+                         (hipStream_t)stream, (const T*)a.dA, (const T*)a.hseq,
+                         (const T*)a.x, a.ws + ws.dwih, a.ws + ws.dwhh, a.ws + ws.db,
+                         R, a.S_pad, a.S, a.Tst, L, a.cin == 1 ? 1 : 0, tpc, fin);
+      return stm_launched();
     });
   });
-}
-
-extern "C" void stmgcn_lstm_wgrad(void* stream, int dtype, const void* dA,
-                                  const void* hseq, const void* x, float* dwih,
-                                  float* dwhh, float* db, long R, long S_pad,
-                                  int S, int Tst, int L, int cin) {
-  lstm_wgrad_launch(stream, dtype, dA, hseq, x, dwih, dwhh, db, R, S_pad, S,
-                    Tst, L, cin, nullptr, nullptr, 0);
-}
-
-extern "C" void stmgcn_lstm_wgrad_grads(void* stream, int dtype, const void* dA,
-                                        const void* hseq, const void* x,
-                                        float* dwih, float* dwhh, float* db,
-                                        unsigned* tickets, void* out, long R,
-                                        long S_pad, int S, int Tst, int L,
-                                        int cin, int gru) {
-  lstm_wgrad_launch(stream, dtype, dA, hseq, x, dwih, dwhh, db, R, S_pad, S,
-                    Tst, L, cin, tickets, out, gru);
 }
 
 // ===========================================================================
@@ -699,56 +674,41 @@ atb_wgrad_kernel(AtbSrc As, int CA, const T* __restrict__ B,
   }
 }
 
-// fin_ticket == null: the accumulate-into form (fp32 sums left in C / db)
-static void atb_wgrad_launch(void* stream, int dtype, const void** As,
-                             int nsrc, int CA, const void* B, float* C,
-                             float* db, long rows, int N, unsigned* fin_ticket,
-                             void* fin_dW, void* fin_db) {
+// a.ws == null: the accumulate-into form (fp32 sums left in a.C / a.db)
+extern "C" const char* stmgcn_atb_wgrad(void* stream, int dtype, const AtbWgradArgs& a) {
+  if (a.nsrc < 1 || a.nsrc > ATB_MAX_SRC) return "stmgcn_atb_wgrad: source count outside 1..4";
   // 256 rows (four K-steps) per workgroup, at most 512 workgroups. At the
   // flagship shape (32768 rows, M = 192, N = 64) that is 128 workgroups and
   // 6.3 MB of float atomics; 128 rows (256 workgroups, twice the atomics) and
   // 512 rows (64 workgroups streaming) both measured slower, in isolation and
   // in the step (profiles/gconv_vector_tiles.md).
+  const long rows = a.rows;
   long nchunks = (rows + 255) / 256;
   if (nchunks > 512) nchunks = 512;
   if (nchunks < 1) nchunks = 1;
   const dim3 grid((unsigned)nchunks), blk(256);
   const size_t lds = 2 * (256 + 64) * 128;   // double-buffered A^T | B^T, 64-row steps
-  const int M = nsrc * CA;
+  const int CA = a.CA, N = a.N, M = a.nsrc * CA;
   AtbSrc src{};
-  for (int i = 0; i < nsrc && i < 4; ++i) src.a[i] = As[i];
-  stm_dispatch_lowp("stmgcn_atb_wgrad", dtype, [&](auto t) {
+  for (int i = 0; i < a.nsrc; ++i) src.a[i] = a.As[i];
+  // finishing form: this launch's rows of the shared workspace and of dW
+  const bool finishing = a.ws != nullptr;
+  const AtbWs ws = atb_ws(a.nsrc_all, CA, N);
+  const long r0 = (long)a.src0 * CA * N;
+  float* C = finishing ? a.ws + ws.C + r0 : a.C;
+  float* db = finishing ? (a.dbo ? a.ws + ws.db : nullptr) : a.db;
+  unsigned* ticket = finishing ? (unsigned*)(a.ws + ws.tickets) + (a.src0 ? 1 : 0) : nullptr;
+  return stm_dispatch_lowp("stmgcn_atb_wgrad: dtype code is not bf16/f16", dtype, [&](auto t) {
     using T = decltype(t);
-    const AtbFin<T> fin{fin_ticket, (T*)fin_dW, (T*)fin_db};
-    stm_dispatch_bool(fin_ticket != nullptr, [&](auto finc) {
-      STM_CHECK_HIP(hipFuncSetAttribute(
-          (const void*)atb_wgrad_kernel<T, decltype(finc)::value>,
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((atb_wgrad_kernel<T, decltype(finc)::value>), grid, blk,
-                         lds, (hipStream_t)stream, src, CA, (const T*)B, C, db,
-                         rows, M, N, fin);
+    const AtbFin<T> fin{ticket, finishing ? (T*)a.dW + r0 : nullptr, (T*)a.dbo};
+    return stm_dispatch_bool(finishing, [&](auto finc) {
+      auto* kernel = atb_wgrad_kernel<T, decltype(finc)::value>;
+      if (const char* e = stm_status(hipFuncSetAttribute(
+              (const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)))
+        return e;
+      hipLaunchKernelGGL(kernel, grid, blk, lds, (hipStream_t)stream, src, CA,
+                         (const T*)a.B, C, db, rows, M, N, fin);
+      return stm_launched();
     });
   });
-}
-
-extern "C" void stmgcn_atb_wgrad_multi(void* stream, int dtype, const void** As,
-                                       int nsrc, int CA, const void* B, float* C,
-                                       float* db, long rows, int N) {
-  atb_wgrad_launch(stream, dtype, As, nsrc, CA, B, C, db, rows, N, nullptr,
-                   nullptr, nullptr);
-}
-
-extern "C" void stmgcn_atb_wgrad_multi_grads(void* stream, int dtype,
-                                             const void** As, int nsrc, int CA,
-                                             const void* B, float* C, float* db,
-                                             unsigned* ticket, void* dW,
-                                             void* dbo, long rows, int N) {
-  atb_wgrad_launch(stream, dtype, As, nsrc, CA, B, C, db, rows, N, ticket, dW,
-                   dbo);
-}
-
-extern "C" void stmgcn_atb_wgrad(void* stream_v, int dtype, const void* A,
-                                 const void* B, float* C, float* db, long rows,
-                                 int M, int N) {
-  stmgcn_atb_wgrad_multi(stream_v, dtype, &A, 1, M, B, C, db, rows, N);
 }
